@@ -11,6 +11,12 @@ update, gain-ratio accept/reject) — the unit the reference logs per
 iteration (MegBA lm_algo.cu "Iter k ... elapsed ms").  Data is synthetic
 (no network for datasets); parameters are ground truth + noise so LM runs a
 realistic trajectory; force_iterations keeps the step count exact.
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line.  `--dump-outputs DIR` also writes the parameters and chi2 the last
+timed step produced as DIR/<name>.npy (inputs are seeded, so two builds can
+be compared output for output).  `--full` adds the side measurements that
+need work of their own (GPU-utilization self-sampling).
 """
 import argparse
 import json
@@ -32,6 +38,40 @@ MODELS = {
 }
 
 
+# --dump-outputs budget: everything written stays under 64 MB in all.
+DUMP_MAX_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(outdir, p, log, rank):
+    """Write the state the last timed lm_step() left behind -- the solved
+    parameters a caller reads back with params() and that step's chi2 -- as
+    float64 .npy files.  params() is collective, so every rank calls this;
+    rank 0 writes.  An array over the byte budget is cut down to a fixed,
+    seeded sample of its rows (sorted row ids go to <name>_rows.npy), the
+    same rows on every run with the same arguments."""
+    import numpy as np
+    cams, pts = p.params()
+    if rank != 0:
+        return
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"cams": np.asarray(cams, dtype=np.float64),
+              "pts": np.asarray(pts, dtype=np.float64)}
+    budget = DUMP_MAX_BYTES // len(arrays)
+    for name, a in arrays.items():
+        if a.nbytes > budget:
+            keep = budget // (a.nbytes // len(a))
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(
+                len(a), size=keep, replace=False))
+            np.save(os.path.join(outdir, name + "_rows.npy"),
+                    rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(outdir, name + ".npy"),
+                np.ascontiguousarray(a))
+    np.save(os.path.join(outdir, "chi2.npy"),
+            np.array([log["chi2"]], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -50,6 +90,13 @@ def main():
     ap.add_argument("--schur", default="implicit",
                     choices=["explicit", "implicit"])
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "left the caller with (cams, pts, chi2) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also collect the side measurements a plain run "
+                         "skips (self-sampled GPU utilization)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
@@ -146,9 +193,9 @@ def main():
             dist.barrier()
 
     # Self-sampled GPU-utilization corroboration (a single
-    # external SMI sample missed the 1-2 s timed region): a background
-    # thread polls rocm-smi during the timed loop; mean/max go into the
-    # JSON line as extra fields.
+    # external SMI sample missed the 1-2 s timed region): with --full a
+    # background thread polls rocm-smi during the timed loop; mean/max go
+    # into the JSON line as extra fields.  A plain run skips it.
     busy_samples = []
     stop_sampling = threading.Event()
 
@@ -170,7 +217,7 @@ def main():
         p.lm_step()
     sync()
     sampler = None
-    if rank == 0 and args.device == "gpu":
+    if args.full and rank == 0 and args.device == "gpu":
         sampler = threading.Thread(target=_sample, daemon=True)
         sampler.start()
     t0 = time.perf_counter()
@@ -190,6 +237,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, p, log, rank)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000.0
