@@ -1629,6 +1629,241 @@ __global__ __launch_bounds__(256) void kFusedLongScatter(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Single-pass Schur apply with an LDS-resident camera accumulator
+// ---------------------------------------------------------------------------
+// kSchurFused reads J once but loses to the two-pass pipeline because its
+// scatter is CD address-divergent GLOBAL atomics per edge.  When the whole
+// camera-side output (CD*ncam values of T) fits one CU's LDS, a persistent
+// workgroup per CU keeps a private copy of it in LDS, scatters with LDS
+// atomics (native ds_add_f64 / ds_add_f32) and writes its copy out once:
+//   - workgroup b of G owns the contiguous window slice
+//     [nWin*b/G, nWin*(b+1)/G) of the run-aligned window table, its waves
+//     stride through the slice (one contiguous stream of the pt-sorted J),
+//   - per window the math is kSchurFused's (t_e, segmented scan, Cinv at the
+//     run tail, tail-mask broadcast); the implicit edge comes from the
+//     PACKED primary (vector-group loads, as kSpmvEtxPk) and stays in
+//     registers for the scatter side,
+//   - flagged windows (segments of >64-edge runs) only add their t
+//     partials to `temp`; kFusedLongW / kFusedLongScatter finish them on
+//     the global output after the flush,
+//   - the flush is plain coalesced stores to row b of rows[G][nc];
+//     kLdsRowsReduce sums the G rows in fixed order and OVERWRITES out, so
+//     the cross-workgroup sum is order-fixed and out needs no memset.
+// A workgroup with an empty slice still zeroes and flushes its row.
+template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
+__global__ __launch_bounds__(1024) void kSchurFusedLds(
+    int nWin, const int64_t* __restrict__ winLo,
+    const int64_t* __restrict__ winHi, const unsigned char* __restrict__ winFlag,
+    int64_t nL, const int* __restrict__ camOf, const int* __restrict__ ptOf,
+    const T* __restrict__ Hpl, const T* __restrict__ Jpk,
+    const T* const* __restrict__ jSlots, const T* __restrict__ info,
+    int lossKind, T lossD2, const T* __restrict__ xPad,
+    const T* __restrict__ HllInv, T* __restrict__ temp, int nc,
+    T* __restrict__ rows) {
+  using TV = typename PackVec<T>::type;
+  constexpr int VEC = PackVec<T>::VEC;
+  constexpr int PP = PD * PD;
+  constexpr int RW = RD * (RD + 1) / 2;
+  constexpr int CR = CD * RD, PR = PD * RD;
+  constexpr int NG = IMP ? (CR + PR + VEC - 1) / VEC
+                         : (CD * PD + VEC - 1) / VEC;
+  constexpr int XP = (CD + VEC - 1) / VEC * VEC;
+  extern __shared__ __align__(16) unsigned char ldsRaw[];
+  T* acc = reinterpret_cast<T*>(ldsRaw);
+  for (int i = (int)threadIdx.x; i < nc; i += (int)blockDim.x) acc[i] = T(0);
+  __syncthreads();
+  const T* rBak = IMP ? jSlots[2] : nullptr;
+  const TV* src = (const TV*)(IMP ? Jpk : Hpl);
+  const int lane = threadIdx.x & 63;
+  const int nWave = (int)blockDim.x >> 6;
+  const int wBeg = (int)((int64_t)nWin * blockIdx.x / gridDim.x);
+  const int wEnd = (int)((int64_t)nWin * (blockIdx.x + 1) / gridDim.x);
+  for (int w = wBeg + ((int)threadIdx.x >> 6); w < wEnd; w += nWave) {
+    const int64_t lo = winLo[w], hi = winHi[w];
+    const bool flagged = winFlag[w] != 0;
+    const bool active = lo + lane < hi;
+    const int64_t j = active ? lo + lane : hi - 1;
+    const int pt = ptOf[j];
+    const int cam = camOf[j];
+    TV buf[NG];
+    T iw[RW];
+    T lw = T(1);
+    T t[PD];
+    for (int k = 0; k < PD; ++k) t[k] = T(0);
+    if (active) {
+      const TV* xv4 = (const TV*)(xPad + (int64_t)cam * XP);
+      TV xbuf[XP / VEC];
+#pragma unroll
+      for (int l = 0; l < XP / VEC; ++l) xbuf[l] = xv4[l];
+#pragma unroll
+      for (int g = 0; g < NG; ++g) buf[g] = src[(int64_t)g * nL + j];
+      if (IMP) {
+        T u[RD];
+#pragma unroll
+        for (int rr = 0; rr < RD; ++rr) {
+          T v = T(0);
+#pragma unroll
+          for (int i = 0; i < CD; ++i) {
+            const int k = i * RD + rr;
+            v += buf[k / VEC][k % VEC] * xbuf[i / VEC][i % VEC];
+          }
+          u[rr] = v;
+        }
+        if (HASINFO) {
+          for (int k = 0; k < RW; ++k) iw[k] = info[RW * j + k];
+          T wu[RD];
+          for (int i = 0; i < RD; ++i) {
+            T v = T(0);
+            for (int k = 0; k < RD; ++k) v += iw[symIdx<RD>(i, k)] * u[k];
+            wu[i] = v;
+          }
+          for (int i = 0; i < RD; ++i) u[i] = wu[i];
+        }
+        if (lossKind) {
+          T ss = T(0);
+          for (int rr = 0; rr < RD; ++rr) {
+            const T rv = rBak[(int64_t)rr * nL + j];
+            ss += rv * rv;
+          }
+          lw = lossWeight(lossKind, lossD2, ss);
+          for (int rr = 0; rr < RD; ++rr) u[rr] *= lw;
+        }
+#pragma unroll
+        for (int k = 0; k < PD; ++k) {
+          T v = T(0);
+#pragma unroll
+          for (int rr = 0; rr < RD; ++rr) {
+            const int kk = CR + k * RD + rr;
+            v += buf[kk / VEC][kk % VEC] * u[rr];
+          }
+          t[k] = v;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < CD; ++i) {
+          const T xi = xbuf[i / VEC][i % VEC];
+#pragma unroll
+          for (int k = 0; k < PD; ++k) {
+            const int kk = i * PD + k;
+            t[k] += buf[kk / VEC][kk % VEC] * xi;
+          }
+        }
+      }
+    }
+    // segmented inclusive scan over the window's point runs
+    for (int off = 1; off < 64; off <<= 1) {
+      const int ppt = __shfl_up(pt, off, 64);
+      const bool join = lane >= off && ppt == pt;
+      if (__ballot(join) == 0ull) break;
+      T a[PD];
+      for (int k = 0; k < PD; ++k) a[k] = __shfl_up(t[k], off, 64);
+      if (join)
+        for (int k = 0; k < PD; ++k) t[k] += a[k];
+    }
+    const int nextPt = __shfl_down(pt, 1, 64);
+    const bool tail = active && (lo + lane == hi - 1 || nextPt != pt);
+    if (flagged) {
+      if (tail)
+        for (int k = 0; k < PD; ++k) atomicAdd(&temp[PD * pt + k], t[k]);
+      continue;
+    }
+    T wv[PD];
+    for (int k = 0; k < PD; ++k) wv[k] = T(0);
+    if (tail) {
+      const T* inv = HllInv + (int64_t)pt * PP;
+      for (int i = 0; i < PD; ++i) {
+        T v = T(0);
+        for (int k = 0; k < PD; ++k) v += inv[i * PD + k] * t[k];
+        wv[i] = v;
+      }
+    }
+    // broadcast w_p from the run tail back to every lane of the run
+    const unsigned long long tails = __ballot(tail);
+    const unsigned long long from = tails >> lane;
+    const int tl = from ? lane + __ffsll((long long)from) - 1 : lane;
+    for (int k = 0; k < PD; ++k) wv[k] = __shfl(wv[k], tl, 64);
+    if (!active) continue;
+    T* oc = acc + cam * CD;
+    if (IMP) {
+      T u[RD];
+#pragma unroll
+      for (int rr = 0; rr < RD; ++rr) {
+        T v = T(0);
+#pragma unroll
+        for (int k = 0; k < PD; ++k) {
+          const int kk = CR + k * RD + rr;
+          v += buf[kk / VEC][kk % VEC] * wv[k];
+        }
+        u[rr] = v;
+      }
+      if (HASINFO) {
+        T wu[RD];
+        for (int i = 0; i < RD; ++i) {
+          T v = T(0);
+          for (int k = 0; k < RD; ++k) v += iw[symIdx<RD>(i, k)] * u[k];
+          wu[i] = v;
+        }
+        for (int i = 0; i < RD; ++i) u[i] = wu[i];
+      }
+      if (lossKind)
+        for (int rr = 0; rr < RD; ++rr) u[rr] *= lw;
+#pragma unroll
+      for (int i = 0; i < CD; ++i) {
+        T v = T(0);
+#pragma unroll
+        for (int rr = 0; rr < RD; ++rr) {
+          const int k = i * RD + rr;
+          v += buf[k / VEC][k % VEC] * u[rr];
+        }
+        atomicAdd(&oc[i], v);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < CD; ++i) {
+        T v = T(0);
+#pragma unroll
+        for (int k = 0; k < PD; ++k) {
+          const int kk = i * PD + k;
+          v += buf[kk / VEC][kk % VEC] * wv[k];
+        }
+        atomicAdd(&oc[i], v);
+      }
+    }
+  }
+  __syncthreads();
+  T* row = rows + (int64_t)blockIdx.x * nc;
+  for (int i = (int)threadIdx.x; i < nc; i += (int)blockDim.x) row[i] = acc[i];
+}
+
+// out[i] = sum over the G workgroup rows, in fixed order (overwrites out).
+// 64 columns per block; each of the block's kLdsRedWaves waves sums a
+// contiguous share of the G rows, and wave 0 combines the shares through
+// LDS in fixed order.
+constexpr int kLdsRedWaves = 16;
+template <typename T>
+__global__ __launch_bounds__(64 * kLdsRedWaves) void kLdsRowsReduce(
+    int G, int nc, const T* __restrict__ rows, T* __restrict__ out) {
+  __shared__ T sm[kLdsRedWaves][64];
+  const int lane = threadIdx.x & 63;
+  const int col = blockIdx.x * 64 + lane;
+  const int q = (int)threadIdx.x >> 6;
+  const int g0 = (int)((int64_t)G * q / kLdsRedWaves);
+  const int g1 = (int)((int64_t)G * (q + 1) / kLdsRedWaves);
+  T s = T(0);
+  if (col < nc) {
+#pragma unroll 8
+    for (int g = g0; g < g1; ++g) s += rows[(int64_t)g * nc + col];
+  }
+  sm[q][lane] = s;
+  __syncthreads();
+  if (q == 0 && col < nc) {
+    T v = sm[0][lane];
+    for (int k = 1; k < kLdsRedWaves; ++k) v += sm[k][lane];
+    out[col] = v;
+  }
+}
+
 // Fused preconditioner apply + rho partial: z = Binv r (thread per row) and
 // per-block partials of r.z in one pass (saves two launches per PCG iter).
 template <typename T, int CD>
@@ -2295,6 +2530,7 @@ class GpuEngine final : public Engine<T> {
       dHpl_ = dalloc<T>(nL_ * NGH * VEC);
       dHplCam_ = dalloc<T>(nL_ * NGH * VEC);
     }
+    setupSchurLds(opt.deviceIndex);
     sync();
   }
 
@@ -2842,17 +3078,49 @@ class GpuEngine final : public Engine<T> {
   // the faster.  Only the LOCAL part runs (no collective), so ranks may
   // even pick differently without breaking lockstep: q partials are
   // per-rank inputs to the allreduce either way.
+  //
+  // The LDS single-pass apply (schurFusedLdsEcE) is a third candidate when
+  // the camera vector fits the per-workgroup LDS limit (setupSchurLds).
+  // MEGBA_SCHUR_LDS forces it on when eligible (also the way problems below
+  // the tuning threshold reach it), MEGBA_NO_SCHUR_LDS removes it; forcing
+  // one of the two-pass variants (MEGBA_NO_ETXFUSE / MEGBA_ETXFUSE) leaves
+  // it out as well.
   void autoTuneEtx() {
     if (etxTuned_) return;
     etxTuned_ = true;
-    if (getenv("MEGBA_NO_ETXFUSE") || getenv("MEGBA_ETXFUSE")) return;
-    if (nL_ < 200000) return;  // launch-noise regime; keep the default
+    chooseSchurPath();
+    // MEGBA_TUNE_VERBOSE reports the choice (the tests read it back)
+    if (getenv("MEGBA_TUNE_VERBOSE"))
+      fprintf(stderr, "# schur path: %s\n",
+              useLds_ ? "lds" : etxFuse_ ? "fused-etx" : "separate");
+  }
+  void chooseSchurPath() {
+    const bool twoPassForced =
+        getenv("MEGBA_NO_ETXFUSE") || getenv("MEGBA_ETXFUSE");
+    const bool ldsForced = getenv("MEGBA_SCHUR_LDS") != nullptr;
+    if (twoPassForced && !ldsForced) ldsEligible_ = false;
+    // nothing to choose: a forced two-pass variant, or the launch-noise
+    // regime, where the default stays
+    if (!ldsForced && (twoPassForced || nL_ < 200000)) return;
+    if (ldsEligible_) {
+      // first launch happens here, outside any graph capture: a launch the
+      // runtime refuses (LDS size) drops the candidate instead of failing
+      (void)hipGetLastError();
+      schurFusedLdsEcE(dDeltaX_, dQ_);
+      if (hipGetLastError() != hipSuccess) ldsEligible_ = false;
+    }
+    if (ldsForced) {
+      useLds_ = ldsEligible_;
+      return;
+    }
     hipEvent_t ev[2];
     HIP_CHECK(hipEventCreate(&ev[0]));
     HIP_CHECK(hipEventCreate(&ev[1]));
-    float ms[2] = {0, 0};
-    for (int variant = 0; variant < 2; ++variant) {
+    float ms[3] = {0, 0, 0};
+    const int nVar = ldsEligible_ ? 3 : 2;
+    for (int variant = 0; variant < nVar; ++variant) {
       etxFuse_ = variant == 0;
+      useLds_ = variant == 2;
       // warm-up then timed triple (dQ_/dWPad_/dTemp_ are scratch)
       localSchurEcE(dDeltaX_, dQ_);
       HIP_CHECK(hipEventRecord(ev[0], stream_));
@@ -2862,11 +3130,117 @@ class GpuEngine final : public Engine<T> {
       HIP_CHECK(hipEventElapsedTime(&ms[variant], ev[0], ev[1]));
     }
     etxFuse_ = ms[0] <= ms[1];
+    useLds_ = ldsEligible_ && ms[2] < (etxFuse_ ? ms[0] : ms[1]);
+    if (getenv("MEGBA_TUNE_VERBOSE"))
+      fprintf(stderr,
+              "# schur autotune: fused-etx %.3f ms, separate %.3f ms, "
+              "lds %.3f ms (3 applies each)\n",
+              ms[0], ms[1], ldsEligible_ ? ms[2] : -1.0f);
     (void)hipEventDestroy(ev[0]);
     (void)hipEventDestroy(ev[1]);
   }
+
+  // Kernel handle of the kSchurFusedLds instance this engine launches.
+  const void* schurLdsKernel() const {
+    if (implicit_ && hasInfo_)
+      return (const void*)kSchurFusedLds<T, CD, PD, RD, true, true>;
+    if (implicit_)
+      return (const void*)kSchurFusedLds<T, CD, PD, RD, true, false>;
+    return (const void*)kSchurFusedLds<T, CD, PD, RD, false, false>;
+  }
+  // Eligibility of the LDS single-pass apply: the camera vector must fit
+  // the runtime's per-workgroup LDS limit (MEGBA_SCHUR_LDS_MAX_BYTES lowers
+  // it for testing) and the kernel's dynamic-LDS attribute must be raised
+  // once, before any graph capture.  Any failure just leaves the existing
+  // paths in charge.
+  void setupSchurLds(int deviceIndex) {
+    ldsEligible_ = false;
+    if (getenv("MEGBA_NO_SCHUR_LDS") || nWin_ == 0) return;
+    int cus = 0, lim = 0, optin = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                              deviceIndex) != hipSuccess ||
+        hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock,
+                              deviceIndex) != hipSuccess) {
+      (void)hipGetLastError();
+      return;
+    }
+    if (hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin,
+                              deviceIndex) != hipSuccess) {
+      (void)hipGetLastError();
+      optin = 0;
+    }
+    int64_t limit = lim > optin ? lim : optin;
+    if (const char* e = getenv("MEGBA_SCHUR_LDS_MAX_BYTES")) {
+      const int64_t cap = atoll(e);
+      if (cap < limit) limit = cap;
+    }
+    const int64_t need = nc_ * (int64_t)sizeof(T);
+    if (cus < 1 || need > limit) return;
+    if (hipFuncSetAttribute(schurLdsKernel(),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)need) != hipSuccess) {
+      (void)hipGetLastError();
+      return;
+    }
+    numCU_ = cus;
+    if (const char* e = getenv("MEGBA_SCHUR_LDS_THREADS")) {
+      // development knob: workgroup size variants (multiple of 64, <=1024)
+      const int n = atoi(e) / 64 * 64;
+      if (n >= 64 && n <= 1024) ldsThreads_ = n;
+    }
+    dLdsRows_ = dalloc<T>((int64_t)numCU_ * nc_);
+    ldsEligible_ = true;
+  }
+
+  // out = E Cinv E^T x (local part) in one pass over the primary-sorted J
+  // with a per-workgroup LDS accumulator; out is fully overwritten.
+  void schurFusedLdsEcE(const T* xv, T* out) {
+    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
+                       stream_, ncam_, xv, dXPad_);
+    if (nLongPts_ > 0)
+      hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
+                         dim3(kBlk), 0, stream_, dTemp_ + (int64_t)ptLo_ * PD,
+                         (int64_t)npL_ * PD);
+    const size_t ldsBytes = (size_t)nc_ * sizeof(T);
+    auto launch = [&](auto impTag, auto infoTag) {
+      constexpr bool IM = decltype(impTag)::value;
+      constexpr bool HI = decltype(infoTag)::value;
+      hipLaunchKernelGGL((kSchurFusedLds<T, CD, PD, RD, IM, HI>),
+                         dim3(numCU_), dim3(ldsThreads_), ldsBytes, stream_,
+                         nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
+                         dPtOf_, dHpl_, dJPk_, (const T* const*)dJSlots_,
+                         dInfo_, lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_,
+                         (int)nc_, dLdsRows_);
+      hipLaunchKernelGGL(kLdsRowsReduce<T>, dim3((int)((nc_ + 63) / 64)),
+                         dim3(64 * kLdsRedWaves), 0, stream_, numCU_,
+                         (int)nc_, dLdsRows_, out);
+      if (nLongPts_ > 0) {
+        hipLaunchKernelGGL((kFusedLongW<T, PD>), dim3(gridFor(nLongPts_)),
+                           dim3(kBlk), 0, stream_, nLongPts_, dLongPts_,
+                           dHllInv_, dTemp_, dW_, PD);
+        const int fg =
+            (nFlagWins_ + 3) / 4 < 8192 ? (nFlagWins_ + 3) / 4 : 8192;
+        hipLaunchKernelGGL((kFusedLongScatter<T, CD, PD, RD, IM, HI>),
+                           dim3(fg < 1 ? 1 : fg), dim3(256), 0, stream_,
+                           nFlagWins_, dFlagWins_, dWinLo_, dWinHi_, nL_,
+                           dCamOf_, dPtOf_, dHpl_,
+                           (const T* const*)dJSlots_, dInfo_, lossKind_,
+                           lossD2_, dXPad_, dW_, out);
+      }
+    };
+    using TrueT = std::integral_constant<bool, true>;
+    using FalseT = std::integral_constant<bool, false>;
+    if (implicit_ && hasInfo_) launch(TrueT{}, TrueT{});
+    else if (implicit_) launch(TrueT{}, FalseT{});
+    else launch(FalseT{}, FalseT{});
+  }
+
   // local (collective-free) E Cinv E^T x into out, current variant
   void localSchurEcE(const T* xv, T* out) {
+    if (useLds_) {
+      schurFusedLdsEcE(xv, out);
+      return;
+    }
     if (etxFuse_) {
       etxCinv(xv);
       spmvEx(dWPad_, out);
@@ -3114,6 +3488,14 @@ class GpuEngine final : public Engine<T> {
   // the real data at the first solve (autoTuneEtx); env overrides force.
   bool etxFuse_ = getenv("MEGBA_NO_ETXFUSE") == nullptr;
   bool etxTuned_ = false;
+  // LDS single-pass Schur apply (kSchurFusedLds): eligible when the camera
+  // vector fits the per-workgroup LDS limit; chosen by autoTuneEtx or
+  // forced with MEGBA_SCHUR_LDS.
+  bool ldsEligible_ = false;
+  bool useLds_ = false;
+  int numCU_ = 0;
+  int ldsThreads_ = 1024;
+  T* dLdsRows_{};  // [numCU_][nc_] per-workgroup flush rows
   int nWin_ = 0, nFlagWins_ = 0, nLongPts_ = 0;
   int64_t* dWinLo_{};
   int64_t* dWinHi_{};
