@@ -57,6 +57,7 @@
 #include "../bal_functor.hpp"
 #include "../jv/jetvector.hpp"
 #include "../smallmat.hpp"
+#include "edge_ops.hpp"
 #include "gpu_engine.hpp"
 
 namespace megba {
@@ -93,13 +94,6 @@ inline int gridFor(int64_t n) {
 // Reductions
 // ---------------------------------------------------------------------------
 enum class ROp { Dot, SumSq, AbsMax };
-
-// 16-byte vector groups used by the packed J / Hpl layouts.
-template <typename T>
-struct PackVec {
-  static constexpr int VEC = 16 / sizeof(T);
-  typedef T type __attribute__((ext_vector_type(16 / sizeof(T))));
-};
 
 template <typename T, ROp OP>
 __global__ void kRedPartial(const T* a, const T* b, int64_t n, double* part) {
@@ -469,13 +463,6 @@ struct SlabLayout {
   static constexpr int SW = JPOFF + (EXPL ? 0 : PD * RD);
 };
 
-// Packed-upper symmetric index for an RDxRD (or PDxPD) matrix.
-template <int D>
-__device__ __host__ constexpr int symIdx(int i, int j) {
-  return i <= j ? i * D - i * (i - 1) / 2 + (j - i)
-                : j * D - j * (j - 1) / 2 + (i - j);
-}
-
 // Per-edge pass, primary ((pt,cam)-sorted) order: Hpl grad-major (for E^T x),
 // the cam-sorted slab row, and the point-side Hll/g_p via a wave-level
 // segmented scan (atomics only at point-run tails).
@@ -619,8 +606,9 @@ __global__ void kAssembleEdge(int64_t nL, const int* __restrict__ camOf,
         gpP[k] = -v;
       }
     }
-    // segmented scan over the wave's point runs (early exit once no lane
-    // continues a segment at this distance — monotone in off)
+    // segmented scan over the wave's point runs: edge_ops.hpp's waveSegScan
+    // written out for the two arrays, because routing it through the helper
+    // lowered this kernel's occupancy (profiles/r04_edge_ops_refactor.md)
     for (int off = 1; off < 64; off <<= 1) {
       const int ppt = __shfl_up(pt, off, 64);
       const bool join = lane >= off && ppt == pt;
@@ -824,7 +812,9 @@ __global__ void kFinalizeCam(int64_t nL, const T* __restrict__ slab,
 // (The standalone kPackJPrimary pass was folded into kAssembleEdge's
 // register writes in r2.)
 
-// Packed E^T x: identical math to kSpmvEtx<IMP>, vector-group loads.
+// Packed E^T x (implicit): kSpmvEtx's run scan over t_e = Jp^T W (Jc x)
+// from the vector-group J.  The accepted r is read through the device
+// pointer slots so a captured graph stays valid across accept-time flips.
 template <typename T, int CD, int PD, int RD, bool HASINFO>
 __global__ void kSpmvEtxPk(int64_t nL, const int* __restrict__ camOf,
                            const int* __restrict__ ptOf,
@@ -899,18 +889,8 @@ __global__ void kSpmvEtxPk(int64_t nL, const int* __restrict__ camOf,
         o[k] = v;
       }
     }
-    for (int off = 1; off < 64; off <<= 1) {
-      const int ppt = __shfl_up(pt, off, 64);
-      const bool join = lane >= off && ppt == pt;
-      if (__ballot(join) == 0ull) break;
-      T a[PD];
-      for (int k = 0; k < PD; ++k) a[k] = __shfl_up(o[k], off, 64);
-      if (join)
-        for (int k = 0; k < PD; ++k) o[k] += a[k];
-    }
-    const int nextPt = __shfl_down(pt, 1, 64);
-    const bool tail = active && (lane == 63 || nextPt != pt || j0 == nL - 1);
-    if (tail)
+    waveSegScan(pt, lane, o);
+    if (runTailTiled(pt, lane, active, j0 == nL - 1))
       for (int k = 0; k < PD; ++k) atomicAdd(&out[PD * pt + k], o[k]);
   }
 }
@@ -927,64 +907,18 @@ __global__ void kSpmvEtxPkAtomic(int64_t nL, const int* __restrict__ camOf,
                                  const T* __restrict__ info, int lossKind,
                                  T lossD2, const T* __restrict__ xPad,
                                  T* __restrict__ out) {
-  using TV = typename PackVec<T>::type;
-  constexpr int VEC = PackVec<T>::VEC;
-  constexpr int RW = RD * (RD + 1) / 2;
-  constexpr int CR = CD * RD, PR = PD * RD;
-  constexpr int NG = (CR + PR + VEC - 1) / VEC;
   const T* rBak = jSlots[2];
   for (int64_t j = blockIdx.x * (int64_t)kBlk + threadIdx.x; j < nL;
        j += (int64_t)gridDim.x * kBlk) {
     const int pt = ptOf[j];
-    constexpr int XP = (CD + VEC - 1) / VEC * VEC;
-    const TV* xv4 = (const TV*)(xPad + (int64_t)camOf[j] * XP);
-    TV xbuf[XP / VEC];
-#pragma unroll
-    for (int l = 0; l < XP / VEC; ++l) xbuf[l] = xv4[l];
-    TV buf[NG];
-    const TV* src = (const TV*)Jpk;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) buf[g] = src[(int64_t)g * nL + j];
-    T u[RD];
-#pragma unroll
-    for (int rr = 0; rr < RD; ++rr) {
-      T v = T(0);
-#pragma unroll
-      for (int i = 0; i < CD; ++i) {
-        const int k = i * RD + rr;
-        v += buf[k / VEC][k % VEC] * xbuf[i / VEC][i % VEC];
-      }
-      u[rr] = v;
-    }
-    if (HASINFO) {
-      T wu[RD];
-      for (int i = 0; i < RD; ++i) {
-        T v = T(0);
-        for (int k = 0; k < RD; ++k)
-          v += info[RW * j + symIdx<RD>(i, k)] * u[k];
-        wu[i] = v;
-      }
-      for (int i = 0; i < RD; ++i) u[i] = wu[i];
-    }
-    if (lossKind) {
-      T ss = T(0);
-      for (int rr = 0; rr < RD; ++rr) {
-        const T rv = rBak[(int64_t)rr * nL + j];
-        ss += rv * rv;
-      }
-      const T w = lossWeight(lossKind, lossD2, ss);
-      for (int rr = 0; rr < RD; ++rr) u[rr] *= w;
-    }
-#pragma unroll
-    for (int k = 0; k < PD; ++k) {
-      T v = T(0);
-#pragma unroll
-      for (int rr = 0; rr < RD; ++rr) {
-        const int kk = CR + k * RD + rr;
-        v += buf[kk / VEC][kk % VEC] * u[rr];
-      }
-      atomicAdd(&out[PD * pt + k], v);
-    }
+    using PE = PackedEdge<T, CD, PD, RD, true>;
+    typename PackVec<T>::type xbuf[PE::NX], buf[PE::NG];
+    loadXPadded<T>(xPad, camOf[j], xbuf);
+    loadGroups<T>(Jpk, nL, j, buf);
+    T t[PD];
+    packedEtx<T, CD, PD, RD, HASINFO>(buf, xbuf, j, nL, info, rBak, lossKind,
+                                      lossD2, t);
+    for (int k = 0; k < PD; ++k) atomicAdd(&out[PD * pt + k], t[k]);
   }
 }
 
@@ -1138,23 +1072,15 @@ __global__ void kInvertJitter(int nBlk, const T* __restrict__ Hd,
 // Schur SpMV pieces
 // ---------------------------------------------------------------------------
 // temp[3*pt] = Hpl^T x per local point (fully local, no collective): one
-// thread per primary-order edge (coalesced grad-major Hpl or J reads; the
+// thread per primary-order edge (coalesced Hpl vector-group reads; the
 // replicated camera vector x is L2-resident), wave segmented-scan over the
-// point runs, atomics only at run tails.  IMP: matrix-free from J
-// (reference C23).
-template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
+// point runs, atomics only at run tails.  Explicit mode only; the
+// matrix-free product is kSpmvEtxPk.
+template <typename T, int CD, int PD, int RD>
 __global__ void kSpmvEtx(int64_t nL, const int* __restrict__ camOf,
                          const int* __restrict__ ptOf,
-                         const T* __restrict__ Hpl,
-                         const T* const* __restrict__ jSlots,
-                         const T* __restrict__ info, int lossKind, T lossD2,
-                         const T* __restrict__ x, T* __restrict__ out) {
-  // IMP reads the accepted J set through the device pointer slots so a
-  // captured graph stays valid across accept-time buffer flips.
-  constexpr int RW = RD * (RD + 1) / 2;
-  const T* Jc = IMP ? jSlots[0] : nullptr;
-  const T* Jp = IMP ? jSlots[1] : nullptr;
-  const T* rBak = IMP ? jSlots[2] : nullptr;
+                         const T* __restrict__ Hpl, const T* __restrict__ x,
+                         T* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int64_t nWork = ((nL + kBlk - 1) / kBlk) * (int64_t)kBlk;
   for (int64_t j0 = blockIdx.x * (int64_t)kBlk + threadIdx.x; j0 < nWork;
@@ -1166,74 +1092,12 @@ __global__ void kSpmvEtx(int64_t nL, const int* __restrict__ camOf,
     for (int k = 0; k < PD; ++k) o[k] = T(0);
     if (active) {
       const T* xc = x + (int64_t)camOf[j] * CD;
-      if (IMP) {
-        T u[RD];
-        for (int rr = 0; rr < RD; ++rr) {
-          T v = T(0);
-          for (int i = 0; i < CD; ++i)
-            v += Jc[((int64_t)(i * RD + rr)) * nL + j] * xc[i];
-          u[rr] = v;
-        }
-        if (HASINFO) {
-          T wu[RD];
-          for (int i = 0; i < RD; ++i) {
-            T v = T(0);
-            for (int k = 0; k < RD; ++k)
-              v += info[RW * j + symIdx<RD>(i, k)] * u[k];
-            wu[i] = v;
-          }
-          for (int i = 0; i < RD; ++i) u[i] = wu[i];
-        }
-        if (lossKind) {
-          T ss = T(0);
-          for (int rr = 0; rr < RD; ++rr) {
-            const T rv = rBak[(int64_t)rr * nL + j];
-            ss += rv * rv;
-          }
-          const T w = lossWeight(lossKind, lossD2, ss);
-          for (int rr = 0; rr < RD; ++rr) u[rr] *= w;
-        }
-        for (int k = 0; k < PD; ++k) {
-          T v = T(0);
-          for (int rr = 0; rr < RD; ++rr)
-            v += Jp[((int64_t)(k * RD + rr)) * nL + j] * u[rr];
-          o[k] = v;
-        }
-      } else {
-        using TV = typename PackVec<T>::type;
-        constexpr int VEC = PackVec<T>::VEC;
-        constexpr int NGH = (CD * PD + VEC - 1) / VEC;
-        TV buf[NGH];
-        const TV* src = (const TV*)Hpl;
-#pragma unroll
-        for (int g = 0; g < NGH; ++g) buf[g] = src[(int64_t)g * nL + j];
-#pragma unroll
-        for (int i = 0; i < CD; ++i) {
-          const T xi = xc[i];
-#pragma unroll
-          for (int k = 0; k < PD; ++k) {
-            const int kk = i * PD + k;
-            o[k] += buf[kk / VEC][kk % VEC] * xi;
-          }
-        }
-      }
+      typename PackVec<T>::type buf[PackedEdge<T, CD, PD, RD, false>::NG];
+      loadGroups<T>(Hpl, nL, j, buf);
+      packedHplTx<T, CD, PD>(buf, [&](int i) { return xc[i]; }, o);
     }
-    for (int off = 1; off < 64; off <<= 1) {
-      const int ppt = __shfl_up(pt, off, 64);
-      const bool join = lane >= off && ppt == pt;
-      // Point runs are short (degree ~5): once no lane continues a segment
-      // at distance `off`, no lane can at any larger distance either — skip
-      // the remaining dependent shuffle rounds (the scan chain is this
-      // kernel's issue-stall bound, 70% SQ_WAIT_INST_ANY).
-      if (__ballot(join) == 0ull) break;
-      T a[PD];
-      for (int k = 0; k < PD; ++k) a[k] = __shfl_up(o[k], off, 64);
-      if (join)
-        for (int k = 0; k < PD; ++k) o[k] += a[k];
-    }
-    const int nextPt = __shfl_down(pt, 1, 64);
-    const bool tail = active && (lane == 63 || nextPt != pt || j0 == nL - 1);
-    if (tail)
+    waveSegScan(pt, lane, o);
+    if (runTailTiled(pt, lane, active, j0 == nL - 1))
       for (int k = 0; k < PD; ++k) atomicAdd(&out[PD * pt + k], o[k]);
   }
 }
@@ -1310,130 +1174,9 @@ __global__ __launch_bounds__(64) void kSpmvEx(
 // their windows only accumulate t partials into `temp` (phase 1 flag);
 // kFusedLongW then applies Cinv for those points and kFusedLongScatter
 // finishes their E-contributions.
-template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
-__device__ inline void fusedLoadEdge(int64_t j, int64_t nL,
-                                     const int* __restrict__ camOf,
-                                     const T* __restrict__ Hpl,
-                                     const T* __restrict__ Jc,
-                                     const T* __restrict__ Jp,
-                                     const T* __restrict__ info,
-                                     const T* __restrict__ rBak, int lossKind,
-                                     T lossD2, const T* __restrict__ xPad,
-                                     T (&jcv)[RD][CD], T (&jpv)[RD][PD],
-                                     T (&hplv)[CD][PD], T (&t)[PD]) {
-  constexpr int RW = RD * (RD + 1) / 2;
-  constexpr int XPV = PackVec<T>::VEC;
-  constexpr int XP = (CD + XPV - 1) / XPV * XPV;
-  const T* xc = xPad + (int64_t)camOf[j] * XP;
-  if (IMP) {
-    for (int i = 0; i < CD; ++i)
-      for (int rr = 0; rr < RD; ++rr)
-        jcv[rr][i] = Jc[((int64_t)(i * RD + rr)) * nL + j];
-    for (int k = 0; k < PD; ++k)
-      for (int rr = 0; rr < RD; ++rr)
-        jpv[rr][k] = Jp[((int64_t)(k * RD + rr)) * nL + j];
-    T u[RD];
-    for (int rr = 0; rr < RD; ++rr) {
-      T v = T(0);
-      for (int i = 0; i < CD; ++i) v += jcv[rr][i] * xc[i];
-      u[rr] = v;
-    }
-    if (HASINFO) {
-      T wu[RD];
-      for (int i = 0; i < RD; ++i) {
-        T v = T(0);
-        for (int k = 0; k < RD; ++k)
-          v += info[RW * j + symIdx<RD>(i, k)] * u[k];
-        wu[i] = v;
-      }
-      for (int i = 0; i < RD; ++i) u[i] = wu[i];
-    }
-    if (lossKind) {
-      T ss = T(0);
-      for (int rr = 0; rr < RD; ++rr) {
-        const T rv = rBak[(int64_t)rr * nL + j];
-        ss += rv * rv;
-      }
-      const T w = lossWeight(lossKind, lossD2, ss);
-      for (int rr = 0; rr < RD; ++rr) u[rr] *= w;
-    }
-    for (int k = 0; k < PD; ++k) {
-      T v = T(0);
-      for (int rr = 0; rr < RD; ++rr) v += jpv[rr][k] * u[rr];
-      t[k] = v;
-    }
-  } else {
-    using TV = typename PackVec<T>::type;
-    constexpr int VEC = PackVec<T>::VEC;
-    constexpr int NGH = (CD * PD + VEC - 1) / VEC;
-    const TV* src = (const TV*)Hpl;
-    TV buf[NGH];
-    for (int g = 0; g < NGH; ++g) buf[g] = src[(int64_t)g * nL + j];
-    for (int i = 0; i < CD; ++i)
-      for (int k = 0; k < PD; ++k) {
-        const int kk = i * PD + k;
-        hplv[i][k] = buf[kk / VEC][kk % VEC];
-      }
-    for (int k = 0; k < PD; ++k) t[k] = T(0);
-    for (int i = 0; i < CD; ++i) {
-      const T xi = xc[i];
-      for (int k = 0; k < PD; ++k) t[k] += hplv[i][k] * xi;
-    }
-  }
-}
-
-// Per-edge E-contribution out[cam] += M w  (M = Jc^T W Jp or Hpl).
-template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
-__device__ inline void fusedScatter(int64_t j, int64_t nL,
-                                    const int* __restrict__ camOf,
-                                    const T* __restrict__ info,
-                                    const T* __restrict__ rBak, int lossKind,
-                                    T lossD2, const T (&jcv)[RD][CD],
-                                    const T (&jpv)[RD][PD],
-                                    const T (&hplv)[CD][PD], const T (&wv)[PD],
-                                    T* __restrict__ out) {
-  constexpr int RW = RD * (RD + 1) / 2;
-  T* oc = out + (int64_t)camOf[j] * CD;
-  if (IMP) {
-    T u[RD];
-    for (int rr = 0; rr < RD; ++rr) {
-      T v = T(0);
-      for (int k = 0; k < PD; ++k) v += jpv[rr][k] * wv[k];
-      u[rr] = v;
-    }
-    if (HASINFO) {
-      T wu[RD];
-      for (int i = 0; i < RD; ++i) {
-        T v = T(0);
-        for (int k = 0; k < RD; ++k)
-          v += info[RW * j + symIdx<RD>(i, k)] * u[k];
-        wu[i] = v;
-      }
-      for (int i = 0; i < RD; ++i) u[i] = wu[i];
-    }
-    if (lossKind) {
-      T ss = T(0);
-      for (int rr = 0; rr < RD; ++rr) {
-        const T rv = rBak[(int64_t)rr * nL + j];
-        ss += rv * rv;
-      }
-      const T w = lossWeight(lossKind, lossD2, ss);
-      for (int rr = 0; rr < RD; ++rr) u[rr] *= w;
-    }
-    for (int i = 0; i < CD; ++i) {
-      T v = T(0);
-      for (int rr = 0; rr < RD; ++rr) v += jcv[rr][i] * u[rr];
-      atomicAdd(&oc[i], v);
-    }
-  } else {
-    for (int i = 0; i < CD; ++i) {
-      T v = T(0);
-      for (int k = 0; k < PD; ++k) v += hplv[i][k] * wv[k];
-      atomicAdd(&oc[i], v);
-    }
-  }
-}
-
+// The per-edge and per-run steps (fusedLoadEdge / fusedScatter, the window
+// scan, Cinv at the tail, the tail broadcast) are in edge_ops.hpp; what is
+// left in each window kernel is its loop and its sink.
 template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
 __global__ __launch_bounds__(256) void kSchurFused(
     int nWin, const int64_t* __restrict__ winLo,
@@ -1460,18 +1203,8 @@ __global__ __launch_bounds__(256) void kSchurFused(
       fusedLoadEdge<T, CD, PD, RD, IMP, HASINFO>(
           j, nL, camOf, Hpl, Jc, Jp, info, rBak, lossKind, lossD2, xPad,
           jcv, jpv, hplv, t);
-    // segmented inclusive scan over the window's point runs
-    for (int off = 1; off < 64; off <<= 1) {
-      const int ppt = __shfl_up(pt, off, 64);
-      const bool join = lane >= off && ppt == pt;
-      if (__ballot(join) == 0ull) break;
-      T a[PD];
-      for (int k = 0; k < PD; ++k) a[k] = __shfl_up(t[k], off, 64);
-      if (join)
-        for (int k = 0; k < PD; ++k) t[k] += a[k];
-    }
-    const int nextPt = __shfl_down(pt, 1, 64);
-    const bool tail = active && (lo + lane == hi - 1 || nextPt != pt);
+    waveSegScan(pt, lane, t);
+    const bool tail = runTailWindow(pt, lane, active, lo, hi);
     if (winFlag[w]) {
       // segment of a >64-edge run: partials only (finished by the long-run
       // kernels)
@@ -1481,21 +1214,8 @@ __global__ __launch_bounds__(256) void kSchurFused(
     }
     T wv[PD];
     for (int k = 0; k < PD; ++k) wv[k] = T(0);
-    if (tail) {
-      const T* inv = HllInv + (int64_t)pt * PP;
-      for (int i = 0; i < PD; ++i) {
-        T v = T(0);
-        for (int k = 0; k < PD; ++k) v += inv[i * PD + k] * t[k];
-        wv[i] = v;
-      }
-    }
-    // broadcast w_p from the run tail back to every lane of the run:
-    // tail lanes form a mask; this lane's tail is the first tail at or
-    // after it (points are sorted within the window).
-    const unsigned long long tails = __ballot(tail);
-    const unsigned long long from = tails >> lane;
-    const int tl = from ? lane + __ffsll((long long)from) - 1 : lane;
-    for (int k = 0; k < PD; ++k) wv[k] = __shfl(wv[k], tl, 64);
+    if (tail) cinvApply<T, PD>(HllInv + (int64_t)pt * PP, t, wv);
+    tailBroadcast(tail, lane, wv);
     if (active)
       fusedScatter<T, CD, PD, RD, IMP, HASINFO>(
           j, nL, camOf, info, rBak, lossKind, lossD2, jcv, jpv, hplv, wv,
@@ -1521,9 +1241,6 @@ __global__ __launch_bounds__(256) void kEtxCinvFused(
     const T* __restrict__ xPad, const T* __restrict__ HllInv,
     T* __restrict__ temp, T* __restrict__ wPad) {
   constexpr int PP = PD * PD;
-  using TV = typename PackVec<T>::type;
-  constexpr int VEC = PackVec<T>::VEC;
-  constexpr int WL = (4 + VEC - 1) / VEC;
   const T* Jc = IMP ? jSlots[0] : nullptr;
   const T* Jp = IMP ? jSlots[1] : nullptr;
   const T* rBak = IMP ? jSlots[2] : nullptr;
@@ -1540,38 +1257,16 @@ __global__ __launch_bounds__(256) void kEtxCinvFused(
       fusedLoadEdge<T, CD, PD, RD, IMP, HASINFO>(
           j, nL, camOf, Hpl, Jc, Jp, info, rBak, lossKind, lossD2, xPad,
           jcv, jpv, hplv, t);
-    for (int off = 1; off < 64; off <<= 1) {
-      const int ppt = __shfl_up(pt, off, 64);
-      const bool join = lane >= off && ppt == pt;
-      if (__ballot(join) == 0ull) break;
-      T a[PD];
-      for (int k = 0; k < PD; ++k) a[k] = __shfl_up(t[k], off, 64);
-      if (join)
-        for (int k = 0; k < PD; ++k) t[k] += a[k];
-    }
-    const int nextPt = __shfl_down(pt, 1, 64);
-    const bool tail = active && (lo + lane == hi - 1 || nextPt != pt);
+    waveSegScan(pt, lane, t);
+    const bool tail = runTailWindow(pt, lane, active, lo, hi);
     if (winFlag[w]) {
       if (tail)
         for (int k = 0; k < PD; ++k) atomicAdd(&temp[PD * pt + k], t[k]);
       continue;
     }
-    if (tail) {
-      const T* inv = HllInv + (int64_t)pt * PP;
-      T out[WL * VEC];
-      for (int k = 0; k < WL * VEC; ++k) out[k] = T(0);
-      for (int i = 0; i < PD; ++i) {
-        T v = T(0);
-        for (int k = 0; k < PD; ++k) v += inv[i * PD + k] * t[k];
-        out[i] = v;
-      }
-      TV* o = (TV*)(wPad + (int64_t)pt * 4);
-      for (int l = 0; l < WL; ++l) {
-        TV v;
-        for (int q = 0; q < VEC; ++q) v[q] = out[l * VEC + q];
-        o[l] = v;
-      }
-    }
+    if (tail)
+      cinvApplyPad<T, PD>(HllInv + (int64_t)pt * PP, t,
+                          wPad + (int64_t)pt * 4);
   }
 }
 
@@ -1586,12 +1281,9 @@ __global__ void kFusedLongW(int nPts, const int* __restrict__ longPts,
   for (int idx = blockIdx.x * (int)blockDim.x + (int)threadIdx.x; idx < nPts;
        idx += (int)gridDim.x * (int)blockDim.x) {
     const int pt = longPts[idx];
-    const T* inv = HllInv + (int64_t)pt * PP;
-    for (int i = 0; i < PD; ++i) {
-      T v = T(0);
-      for (int k = 0; k < PD; ++k) v += inv[i * PD + k] * temp[PD * pt + k];
-      w[(int64_t)wStride * pt + i] = v;
-    }
+    const T* tp = temp + PD * pt;
+    T* wp = w + (int64_t)wStride * pt;
+    cinvApply<T, PD>(HllInv + (int64_t)pt * PP, tp, wp);
   }
 }
 
@@ -1944,27 +1636,9 @@ __global__ void kBlockDiagMatVec(int nBlk, const T* __restrict__ A,
 template <typename T, int PD>
 __global__ void kCinvPad(int nBlk, const T* __restrict__ A,
                          const T* __restrict__ x, T* __restrict__ yPad) {
-  using TV = typename PackVec<T>::type;
-  constexpr int VEC = PackVec<T>::VEC;
-  constexpr int WL = (4 + VEC - 1) / VEC;
   for (int64_t b = blockIdx.x * (int64_t)kBlk + threadIdx.x; b < nBlk;
-       b += (int64_t)gridDim.x * kBlk) {
-    const T* inv = A + b * PD * PD;
-    const T* xb = x + b * PD;
-    T out[WL * VEC];
-    for (int k = 0; k < WL * VEC; ++k) out[k] = T(0);
-    for (int i = 0; i < PD; ++i) {
-      T sv = T(0);
-      for (int j = 0; j < PD; ++j) sv += inv[i * PD + j] * xb[j];
-      out[i] = sv;
-    }
-    TV* o = (TV*)(yPad + b * 4);
-    for (int l = 0; l < WL; ++l) {
-      TV v;
-      for (int q = 0; q < VEC; ++q) v[q] = out[l * VEC + q];
-      o[l] = v;
-    }
-  }
+       b += (int64_t)gridDim.x * kBlk)
+    cinvApplyPad<T, PD>(A + b * PD * PD, x + b * PD, yPad + b * 4);
 }
 
 // Pad the CD-stride camera vector to a 16B-aligned XP stride (one vector
@@ -2170,38 +1844,24 @@ __global__ void kRhoDenomPk(int64_t nL, const int* __restrict__ camOf,
                             const T* __restrict__ dxcPad,
                             const T* __restrict__ dxp, double* acc,
                             int lossKind, T lossD2) {
-  using TV = typename PackVec<T>::type;
-  constexpr int VEC = PackVec<T>::VEC;
-  constexpr int CR = CD * RD, PR = PD * RD;
-  constexpr int NG = (CR + PR + VEC - 1) / VEC;
-  constexpr int XP = (CD + VEC - 1) / VEC * VEC;
   __shared__ double sm[kBlk];
   double local = 0.0;
-  const TV* src = (const TV*)Jpk;
   for (int64_t e = blockIdx.x * (int64_t)kBlk + threadIdx.x; e < nL;
        e += (int64_t)gridDim.x * kBlk) {
-    const TV* xv4 = (const TV*)(dxcPad + (int64_t)camOf[e] * XP);
-    TV xbuf[XP / VEC];
-#pragma unroll
-    for (int l = 0; l < XP / VEC; ++l) xbuf[l] = xv4[l];
-    TV buf[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) buf[g] = src[(int64_t)g * nL + e];
+    using PE = PackedEdge<T, CD, PD, RD, true>;
+    typename PackVec<T>::type xbuf[PE::NX], buf[PE::NG];
+    loadXPadded<T>(dxcPad, camOf[e], xbuf);
+    loadGroups<T>(Jpk, nL, e, buf);
     const T* dp = dxp + (int64_t)ptOf[e] * PD;
     T ss = T(0);
 #pragma unroll
     for (int row = 0; row < RD; ++row) {
       T sv = r[(int64_t)row * nL + e];
 #pragma unroll
-      for (int k = 0; k < CD; ++k) {
-        const int kk = k * RD + row;
-        sv += buf[kk / VEC][kk % VEC] * xbuf[k / VEC][k % VEC];
-      }
+      for (int k = 0; k < CD; ++k)
+        sv += pkJc<T, RD>(buf, k, row) * pkX<T>(xbuf, k);
 #pragma unroll
-      for (int k = 0; k < PD; ++k) {
-        const int kk = CR + k * RD + row;
-        sv += buf[kk / VEC][kk % VEC] * dp[k];
-      }
+      for (int k = 0; k < PD; ++k) sv += pkJp<T, CD, RD>(buf, k, row) * dp[k];
       ss += sv * sv;
     }
     local += (double)lossRho(lossKind, lossD2, ss);
@@ -3140,13 +2800,59 @@ class GpuEngine final : public Engine<T> {
     (void)hipEventDestroy(ev[1]);
   }
 
+  // f(impTag, infoTag) with this engine's (implicit_, hasInfo_) as
+  // integral_constant tags: the three combinations the product kernels are
+  // instantiated for (the explicit Hpl already carries the weights).
+  template <typename F>
+  decltype(auto) dispatchMode(F&& f) const {
+    using TrueT = std::integral_constant<bool, true>;
+    using FalseT = std::integral_constant<bool, false>;
+    if (implicit_ && hasInfo_) return f(TrueT{}, TrueT{});
+    if (implicit_) return f(TrueT{}, FalseT{});
+    return f(FalseT{}, FalseT{});
+  }
   // Kernel handle of the kSchurFusedLds instance this engine launches.
   const void* schurLdsKernel() const {
-    if (implicit_ && hasInfo_)
-      return (const void*)kSchurFusedLds<T, CD, PD, RD, true, true>;
-    if (implicit_)
-      return (const void*)kSchurFusedLds<T, CD, PD, RD, true, false>;
-    return (const void*)kSchurFusedLds<T, CD, PD, RD, false, false>;
+    return dispatchMode([](auto im, auto hi) {
+      return (const void*)kSchurFusedLds<T, CD, PD, RD, decltype(im)::value,
+                                         decltype(hi)::value>;
+    });
+  }
+  // Grid of the one-wave-per-window kernels (4 waves per block).
+  static int windowGrid(int nWin) {
+    const int g = (nWin + 3) / 4 < 8192 ? (nWin + 3) / 4 : 8192;
+    return g < 1 ? 1 : g;
+  }
+  // Common start of the window passes: the XP-padded copy of x, and a zeroed
+  // temp when >64-edge runs will add partials to it.
+  void windowPrologue(const T* xv) {
+    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
+                       stream_, ncam_, xv, dXPad_);
+    if (nLongPts_ > 0)
+      hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
+                         dim3(kBlk), 0, stream_, dTemp_ + (int64_t)ptLo_ * PD,
+                         (int64_t)npL_ * PD);
+  }
+  // w_p = Cinv temp_p for the >64-edge points, into w at the given stride.
+  void longRunW(T* w, int stride) {
+    if (nLongPts_ > 0)
+      hipLaunchKernelGGL((kFusedLongW<T, PD>), dim3(gridFor(nLongPts_)),
+                         dim3(kBlk), 0, stream_, nLongPts_, dLongPts_,
+                         dHllInv_, dTemp_, w, stride);
+  }
+  // Finish the flagged windows of a single-pass apply on the global output.
+  void finishLongRuns(T* out) {
+    if (nLongPts_ == 0) return;
+    longRunW(dW_, PD);
+    dispatchMode([&](auto impTag, auto infoTag) {
+      constexpr bool IM = decltype(impTag)::value;
+      constexpr bool HI = decltype(infoTag)::value;
+      hipLaunchKernelGGL((kFusedLongScatter<T, CD, PD, RD, IM, HI>),
+                         dim3(windowGrid(nFlagWins_)), dim3(256), 0, stream_,
+                         nFlagWins_, dFlagWins_, dWinLo_, dWinHi_, nL_,
+                         dCamOf_, dPtOf_, dHpl_, (const T* const*)dJSlots_,
+                         dInfo_, lossKind_, lossD2_, dXPad_, dW_, out);
+    });
   }
   // Eligibility of the LDS single-pass apply: the camera vector must fit
   // the runtime's per-workgroup LDS limit (MEGBA_SCHUR_LDS_MAX_BYTES lowers
@@ -3195,14 +2901,9 @@ class GpuEngine final : public Engine<T> {
   // out = E Cinv E^T x (local part) in one pass over the primary-sorted J
   // with a per-workgroup LDS accumulator; out is fully overwritten.
   void schurFusedLdsEcE(const T* xv, T* out) {
-    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                       stream_, ncam_, xv, dXPad_);
-    if (nLongPts_ > 0)
-      hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
-                         dim3(kBlk), 0, stream_, dTemp_ + (int64_t)ptLo_ * PD,
-                         (int64_t)npL_ * PD);
+    windowPrologue(xv);
     const size_t ldsBytes = (size_t)nc_ * sizeof(T);
-    auto launch = [&](auto impTag, auto infoTag) {
+    dispatchMode([&](auto impTag, auto infoTag) {
       constexpr bool IM = decltype(impTag)::value;
       constexpr bool HI = decltype(infoTag)::value;
       hipLaunchKernelGGL((kSchurFusedLds<T, CD, PD, RD, IM, HI>),
@@ -3211,28 +2912,11 @@ class GpuEngine final : public Engine<T> {
                          dPtOf_, dHpl_, dJPk_, (const T* const*)dJSlots_,
                          dInfo_, lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_,
                          (int)nc_, dLdsRows_);
-      hipLaunchKernelGGL(kLdsRowsReduce<T>, dim3((int)((nc_ + 63) / 64)),
-                         dim3(64 * kLdsRedWaves), 0, stream_, numCU_,
-                         (int)nc_, dLdsRows_, out);
-      if (nLongPts_ > 0) {
-        hipLaunchKernelGGL((kFusedLongW<T, PD>), dim3(gridFor(nLongPts_)),
-                           dim3(kBlk), 0, stream_, nLongPts_, dLongPts_,
-                           dHllInv_, dTemp_, dW_, PD);
-        const int fg =
-            (nFlagWins_ + 3) / 4 < 8192 ? (nFlagWins_ + 3) / 4 : 8192;
-        hipLaunchKernelGGL((kFusedLongScatter<T, CD, PD, RD, IM, HI>),
-                           dim3(fg < 1 ? 1 : fg), dim3(256), 0, stream_,
-                           nFlagWins_, dFlagWins_, dWinLo_, dWinHi_, nL_,
-                           dCamOf_, dPtOf_, dHpl_,
-                           (const T* const*)dJSlots_, dInfo_, lossKind_,
-                           lossD2_, dXPad_, dW_, out);
-      }
-    };
-    using TrueT = std::integral_constant<bool, true>;
-    using FalseT = std::integral_constant<bool, false>;
-    if (implicit_ && hasInfo_) launch(TrueT{}, TrueT{});
-    else if (implicit_) launch(TrueT{}, FalseT{});
-    else launch(FalseT{}, FalseT{});
+    });
+    hipLaunchKernelGGL(kLdsRowsReduce<T>, dim3((int)((nc_ + 63) / 64)),
+                       dim3(64 * kLdsRedWaves), 0, stream_, numCU_, (int)nc_,
+                       dLdsRows_, out);
+    finishLongRuns(out);
   }
 
   // local (collective-free) E Cinv E^T x into out, current variant
@@ -3263,42 +2947,25 @@ class GpuEngine final : public Engine<T> {
     hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
                        dim3(kBlk), 0, stream_, out + (int64_t)ptLo_ * PD,
                        (int64_t)npL_ * PD);
-    if (implicit_) {
-      // 16B-aligned padded copy of x: the per-edge camera gather becomes
-      // XP/VEC vector loads instead of CD divergent scalar loads.
-      hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk),
-                         0, stream_, ncam_, xv, dXPad_);
-      if (etxAtomic_) {
-        if (hasInfo_)
-          hipLaunchKernelGGL((kSpmvEtxPkAtomic<T, CD, PD, RD, true>),
-                             dim3(gridFor(nL_)), dim3(kBlk), 0, stream_, nL_,
-                             dCamOf_, dPtOf_, dJPk_,
-                             (const T* const*)dJSlots_, dInfo_, lossKind_,
-                             lossD2_, dXPad_, out);
-        else
-          hipLaunchKernelGGL((kSpmvEtxPkAtomic<T, CD, PD, RD, false>),
-                             dim3(gridFor(nL_)), dim3(kBlk), 0, stream_, nL_,
-                             dCamOf_, dPtOf_, dJPk_,
-                             (const T* const*)dJSlots_, (const T*)nullptr,
-                             lossKind_, lossD2_, dXPad_, out);
-      } else if (hasInfo_)
-        hipLaunchKernelGGL((kSpmvEtxPk<T, CD, PD, RD, true>),
-                           dim3(gridFor(nL_)), dim3(kBlk), 0, stream_, nL_,
-                           dCamOf_, dPtOf_, dJPk_,
-                           (const T* const*)dJSlots_, dInfo_, lossKind_,
-                           lossD2_, dXPad_, out);
-      else
-        hipLaunchKernelGGL((kSpmvEtxPk<T, CD, PD, RD, false>),
-                           dim3(gridFor(nL_)), dim3(kBlk), 0, stream_, nL_,
-                           dCamOf_, dPtOf_, dJPk_,
-                           (const T* const*)dJSlots_, (const T*)nullptr,
-                           lossKind_, lossD2_, dXPad_, out);
-    } else {
-      hipLaunchKernelGGL((kSpmvEtx<T, CD, PD, RD, false, false>),
-                         dim3(gridFor(nL_)), dim3(kBlk), 0, stream_, nL_,
-                         dCamOf_, dPtOf_, dHpl_, (const T* const*)nullptr,
-                         (const T*)nullptr, 0, T(0), xv, out);
+    if (!implicit_) {
+      hipLaunchKernelGGL((kSpmvEtx<T, CD, PD, RD>), dim3(gridFor(nL_)),
+                         dim3(kBlk), 0, stream_, nL_, dCamOf_, dPtOf_, dHpl_,
+                         xv, out);
+      return;
     }
+    // 16B-aligned padded copy of x: the per-edge camera gather becomes
+    // XP/VEC vector loads instead of CD divergent scalar loads.
+    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
+                       stream_, ncam_, xv, dXPad_);
+    dispatchMode([&](auto, auto infoTag) {
+      constexpr bool HI = decltype(infoTag)::value;
+      const auto kernel = etxAtomic_ ? kSpmvEtxPkAtomic<T, CD, PD, RD, HI>
+                                     : kSpmvEtxPk<T, CD, PD, RD, HI>;
+      hipLaunchKernelGGL(kernel, dim3(gridFor(nL_)), dim3(kBlk), 0, stream_,
+                         nL_, dCamOf_, dPtOf_, dJPk_,
+                         (const T* const*)dJSlots_, dInfo_, lossKind_,
+                         lossD2_, dXPad_, out);
+    });
   }
   void spmvEx(const T* wv, T* out) {
     HIP_CHECK(hipMemsetAsync(out, 0, nc_ * sizeof(T), stream_));
@@ -3378,71 +3045,34 @@ class GpuEngine final : public Engine<T> {
   // negative, kept env-gated).
   void schurFusedEcE(const T* xv, T* out) {
     HIP_CHECK(hipMemsetAsync(out, 0, nc_ * sizeof(T), stream_));
-    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                       stream_, ncam_, xv, dXPad_);
-    if (nLongPts_ > 0)
-      hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
-                         dim3(kBlk), 0, stream_, dTemp_ + (int64_t)ptLo_ * PD,
-                         (int64_t)npL_ * PD);
-    const int grid = (nWin_ + 3) / 4 < 8192 ? (nWin_ + 3) / 4 : 8192;
-    auto launch = [&](auto impTag, auto infoTag) {
+    windowPrologue(xv);
+    dispatchMode([&](auto impTag, auto infoTag) {
       constexpr bool IM = decltype(impTag)::value;
       constexpr bool HI = decltype(infoTag)::value;
       hipLaunchKernelGGL((kSchurFused<T, CD, PD, RD, IM, HI>),
-                         dim3(grid < 1 ? 1 : grid), dim3(256), 0, stream_,
+                         dim3(windowGrid(nWin_)), dim3(256), 0, stream_,
                          nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
                          dPtOf_, dHpl_, (const T* const*)dJSlots_, dInfo_,
                          lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_, out);
-      if (nLongPts_ > 0) {
-        hipLaunchKernelGGL((kFusedLongW<T, PD>), dim3(gridFor(nLongPts_)),
-                           dim3(kBlk), 0, stream_, nLongPts_, dLongPts_,
-                           dHllInv_, dTemp_, dW_, PD);
-        const int fg =
-            (nFlagWins_ + 3) / 4 < 8192 ? (nFlagWins_ + 3) / 4 : 8192;
-        hipLaunchKernelGGL((kFusedLongScatter<T, CD, PD, RD, IM, HI>),
-                           dim3(fg < 1 ? 1 : fg), dim3(256), 0, stream_,
-                           nFlagWins_, dFlagWins_, dWinLo_, dWinHi_, nL_,
-                           dCamOf_, dPtOf_, dHpl_,
-                           (const T* const*)dJSlots_, dInfo_, lossKind_,
-                           lossD2_, dXPad_, dW_, out);
-      }
-    };
-    using TrueT = std::integral_constant<bool, true>;
-    using FalseT = std::integral_constant<bool, false>;
-    if (implicit_ && hasInfo_) launch(TrueT{}, TrueT{});
-    else if (implicit_) launch(TrueT{}, FalseT{});
-    else launch(FalseT{}, FalseT{});
+    });
+    finishLongRuns(out);
   }
 
   // w = Cinv E^T x into the 4-padded w vector, one fused window pass
   // (default path; see kEtxCinvFused).
   void etxCinv(const T* xv) {
-    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                       stream_, ncam_, xv, dXPad_);
-    if (nLongPts_ > 0)
-      hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
-                         dim3(kBlk), 0, stream_, dTemp_ + (int64_t)ptLo_ * PD,
-                         (int64_t)npL_ * PD);
-    const int grid = (nWin_ + 3) / 4 < 8192 ? (nWin_ + 3) / 4 : 8192;
-    auto launch = [&](auto impTag, auto infoTag) {
+    windowPrologue(xv);
+    dispatchMode([&](auto impTag, auto infoTag) {
       constexpr bool IM = decltype(impTag)::value;
       constexpr bool HI = decltype(infoTag)::value;
       hipLaunchKernelGGL((kEtxCinvFused<T, CD, PD, RD, IM, HI>),
-                         dim3(grid < 1 ? 1 : grid), dim3(256), 0, stream_,
+                         dim3(windowGrid(nWin_)), dim3(256), 0, stream_,
                          nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
                          dPtOf_, dHpl_, (const T* const*)dJSlots_, dInfo_,
                          lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_,
                          dWPad_);
-      if (nLongPts_ > 0)
-        hipLaunchKernelGGL((kFusedLongW<T, PD>), dim3(gridFor(nLongPts_)),
-                           dim3(kBlk), 0, stream_, nLongPts_, dLongPts_,
-                           dHllInv_, dTemp_, dWPad_, 4);
-    };
-    using TrueT = std::integral_constant<bool, true>;
-    using FalseT = std::integral_constant<bool, false>;
-    if (implicit_ && hasInfo_) launch(TrueT{}, TrueT{});
-    else if (implicit_) launch(TrueT{}, FalseT{});
-    else launch(FalseT{}, FalseT{});
+    });
+    longRunW(dWPad_, 4);
   }
 
   // q = S x = HppD x - E Cinv E^T x  (ONE CD*ncam allreduce; the reference's

@@ -121,8 +121,8 @@ def test_lds_starved_grid(capfd):
     _pair(capfd, "implicit", mb.synthesize_bal(6, 40, 240, seed=3))
 
 
-def test_lds_other_block_dims(capfd):
-    """(6,3,2): the LDS index cam*CD+i with CD != 9."""
+def _dims632_problem():
+    """(6,3,2) problem with shared intrinsics: (args, intrinsics)."""
     intr = [420.0, -1e-7, 3e-13]
     cams9, pts, ci, pi, meas0 = mb.synthesize_bal(12, 110, 950, seed=12)
     cams9[:, 6:9] = intr
@@ -134,7 +134,12 @@ def test_lds_other_block_dims(capfd):
     r = np.empty_like(r_sorted)
     r[p.index_info()["perm"]] = r_sorted
     meas = r + np.random.default_rng(112).normal(0, 0.5, r.shape)
-    args = (cams9[:, :6].copy(), pts, ci, pi, meas)
+    return (cams9[:, :6].copy(), pts, ci, pi, meas), intr
+
+
+def test_lds_other_block_dims(capfd):
+    """(6,3,2): the LDS index cam*CD+i with CD != 9."""
+    args, intr = _dims632_problem()
     for schur in ("explicit", "implicit"):
         _pair(capfd, schur, args, intrinsics=intr)
 
@@ -220,3 +225,78 @@ def test_lds_fp32(capfd):
     dev = np.abs(dx2 - dx1).max() / scale
     print("fp32 lds-vs-default deviation / max|deltaX|:", dev)
     assert dev <= FP32_BOUND
+
+
+# ---------------------------------------------------------------------------
+# Separate-pass path (MEGBA_NO_ETXFUSE=1: kSpmvEtx / kSpmvEtxPk + kCinvPad)
+# and its scan-free E^T x variant (MEGBA_ETX_ATOMIC=1: kSpmvEtxPkAtomic),
+# value-checked against the default path like the LDS cases above.
+# ---------------------------------------------------------------------------
+SEP = {"MEGBA_NO_ETXFUSE": "1"}
+SEP_ATOMIC = {"MEGBA_NO_ETXFUSE": "1", "MEGBA_ETX_ATOMIC": "1"}
+
+
+def _sep_pair(capfd, schur, args, env=SEP, **kw):
+    _pair(capfd, schur, args, lds_env=env, expect="separate", **kw)
+
+
+@pytest.mark.parametrize("schur", ["explicit", "implicit"])
+def test_separate_matches_default(capfd, schur):
+    _sep_pair(capfd, schur, mb.synthesize_bal(24, 400, 3600, seed=14))
+
+
+@pytest.mark.parametrize("schur", ["explicit", "implicit"])
+def test_separate_long_run_point(capfd, schur):
+    """A >64-edge run crosses wave edges in the block-tiled scan."""
+    _sep_pair(capfd, schur, _long_run_problem())
+
+
+def test_separate_weighted_info(capfd):
+    args, info = _weighted_problem()
+    _sep_pair(capfd, "implicit", args, info=info)
+
+
+def test_separate_robust_loss(capfd):
+    args, info = _weighted_problem()
+    _sep_pair(capfd, "implicit", args, info=info, loss="huber",
+              loss_delta=1.5)
+
+
+@pytest.mark.parametrize("schur", ["explicit", "implicit"])
+def test_separate_other_block_dims(capfd, schur):
+    args, intr = _dims632_problem()
+    _sep_pair(capfd, schur, args, intrinsics=intr)
+
+
+def test_separate_atomic_matches_default(capfd):
+    _sep_pair(capfd, "implicit", mb.synthesize_bal(24, 400, 3600, seed=14),
+              env=SEP_ATOMIC)
+
+
+def test_separate_atomic_robust_loss(capfd):
+    args, info = _weighted_problem()
+    _sep_pair(capfd, "implicit", args, env=SEP_ATOMIC, info=info,
+              loss="huber", loss_delta=1.5)
+
+
+# fp32, separate vs default: the bound comes from the code before the shared
+# edge primitives existed.  There the separate-pass path and the default
+# path differ on this problem by FP32_SEP_PARENT_DEV * max|deltaX| (measured
+# on MI355X: 6.5575e-5, with max|deltaX| = 1.878); the separate path is
+# allowed four times that, 2.6230e-4.
+FP32_SEP_PARENT_DEV = 6.5575e-5
+FP32_SEP_BOUND = 4 * FP32_SEP_PARENT_DEV
+
+
+def test_separate_fp32(capfd):
+    args = mb.synthesize_bal(24, 400, 3600, seed=14)
+    capfd.readouterr()
+    n1, dx1 = _solve({}, "implicit", args, dtype="float32")
+    n2, dx2 = _solve(SEP, "implicit", args, dtype="float32")
+    assert _path(capfd) == ["fused-etx", "separate"]
+    assert n1 == n2
+    scale = np.abs(dx1).max() or 1.0
+    dev = np.abs(dx2 - dx1).max() / scale
+    print("fp32 separate-vs-default deviation / max|deltaX|:", dev,
+          "max|deltaX|:", scale)
+    assert dev <= FP32_SEP_BOUND
