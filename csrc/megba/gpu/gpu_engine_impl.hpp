@@ -1388,8 +1388,13 @@ __global__ __launch_bounds__(1024) void kSchurFusedLds(
       TV xbuf[XP / VEC];
 #pragma unroll
       for (int l = 0; l < XP / VEC; ++l) xbuf[l] = xv4[l];
+      // The packed groups are read once per apply, by one lane each, so they
+      // are loaded non-temporal: the intent is that the stream leaves what
+      // every apply re-reads (HllInv, camOf/ptOf, the rows) in the last-level
+      // cache.  Measured on Venice in profiles/r05_pcg_fusion.md.
 #pragma unroll
-      for (int g = 0; g < NG; ++g) buf[g] = src[(int64_t)g * nL + j];
+      for (int g = 0; g < NG; ++g)
+        buf[g] = __builtin_nontemporal_load(&src[(int64_t)g * nL + j]);
       if (IMP) {
         T u[RD];
 #pragma unroll
@@ -1753,6 +1758,160 @@ __global__ void kUpdateXRAlpha(int64_t n, const double* __restrict__ partR,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Rotated PCG body: three small kernels around the product instead of six
+// ---------------------------------------------------------------------------
+// The loop is rotated by one kernel (z = Binv r and its rho partials move to
+// the end of the previous body; the first ones come from a kPrecondRho
+// before the loop), so neighbours that work on the same camera blocks merge:
+//   kBetaPPad          = kXpbySBeta + kPadX
+//   kLdsReduceBApplyDot = kLdsRowsReduce + kBApplyDot
+//   kUpdateXRPrecond   = kUpdateXRAlpha + kPrecondRho
+
+// beta + p-update (as kXpbySBeta) that also writes the XP-padded copy of the
+// new p in kPadX's layout, zero pad lanes included.  One thread per padded
+// element.
+template <typename T, int CD>
+__global__ void kBetaPPad(int ncam, const T* __restrict__ z,
+                          const double* __restrict__ part, int nb,
+                          const double* __restrict__ rhoPrev,
+                          double* __restrict__ rhoOut, T* __restrict__ p,
+                          T* __restrict__ xPad) {
+  constexpr int VEC = PackVec<T>::VEC;
+  constexpr int XP = (CD + VEC - 1) / VEC * VEC;
+  __shared__ double sm[kBlk];
+  double v = 0.0;
+  for (int i = threadIdx.x; i < nb; i += kBlk) v += part[i];
+  sm[threadIdx.x] = v;
+  __syncthreads();
+  for (int st = kBlk / 2; st > 0; st >>= 1) {
+    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
+    __syncthreads();
+  }
+  const double rho = sm[0];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *rhoOut = rho;
+  const double rp = *rhoPrev;
+  const T beta = (T)(rp != 0.0 ? rho / rp : 0.0);
+  for (int64_t idx = blockIdx.x * (int64_t)kBlk + threadIdx.x;
+       idx < (int64_t)ncam * XP; idx += (int64_t)gridDim.x * kBlk) {
+    const int64_t c = idx / XP;
+    const int k = (int)(idx % XP);
+    T pv = T(0);
+    if (k < CD) {
+      const int64_t i = c * CD + k;
+      pv = z[i] + beta * p[i];
+      p[i] = pv;
+    }
+    xPad[idx] = pv;
+  }
+}
+
+// kLdsRowsReduce whose wave 0 goes on to the B-apply and the p.q partial:
+// out = HppD p - (fixed-order sum of the G rows), one partial per block.
+// p is read-only here, so a camera that straddles a 64-column block edge is
+// read by both blocks.  Only valid when nothing (long-run finishers,
+// allreduce) sits between the row reduce and the B-apply.
+template <typename T, int CD>
+__global__ __launch_bounds__(64 * kLdsRedWaves) void kLdsReduceBApplyDot(
+    int G, int nc, const T* __restrict__ rows, const T* __restrict__ A,
+    const T* __restrict__ p, T* __restrict__ out, double* __restrict__ part) {
+  __shared__ T sm[kLdsRedWaves][64];
+  const int lane = threadIdx.x & 63;
+  const int col = blockIdx.x * 64 + lane;
+  const int q = (int)threadIdx.x >> 6;
+  const int g0 = (int)((int64_t)G * q / kLdsRedWaves);
+  const int g1 = (int)((int64_t)G * (q + 1) / kLdsRedWaves);
+  T s = T(0);
+  if (col < nc) {
+#pragma unroll 8
+    for (int g = g0; g < g1; ++g) s += rows[(int64_t)g * nc + col];
+  }
+  sm[q][lane] = s;
+  __syncthreads();
+  if (q != 0) return;
+  double local = 0.0;
+  if (col < nc) {
+    T v = sm[0][lane];
+    for (int k = 1; k < kLdsRedWaves; ++k) v += sm[k][lane];
+    const int b = col / CD;
+    const int rrow = col % CD;
+    const T* row = A + (int64_t)b * CD * CD + rrow * CD;
+    const T* xb = p + (int64_t)b * CD;
+    T hp = T(0);
+    for (int j = 0; j < CD; ++j) hp += row[j] * xb[j];
+    const T qv = hp - v;
+    out[col] = qv;
+    local = (double)p[col] * (double)qv;
+  }
+  for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+  if (lane == 0) part[blockIdx.x] = local;
+}
+
+// alpha + x/r update (as kUpdateXRAlpha, backup rotation included) followed
+// by the NEXT iteration's z = Binv r and rho partials (as kPrecondRho).
+// Each block owns kBlk / CD whole cameras and hands r_new to the threads of
+// the same camera through LDS, so r is never re-read from global memory
+// while other threads store to it.  rho is the scalar the beta kernel
+// published (every block of that kernel reduces the same partials in the
+// same order), which leaves `part` free for the new partials.
+template <typename T, int CD>
+__global__ __launch_bounds__(kBlk) void kUpdateXRPrecond(
+    int ncam, const double* __restrict__ rhoIn,
+    const double* __restrict__ partQ, int nbQ,
+    double* __restrict__ rhoPrevOut, const T* __restrict__ p,
+    const T* __restrict__ q, T* __restrict__ x, T* __restrict__ xBak,
+    T* __restrict__ xBakPrev, T* __restrict__ r, const T* __restrict__ Binv,
+    T* __restrict__ z, double* __restrict__ part) {
+  constexpr int CPB = kBlk / CD;  // cameras per block
+  __shared__ double sm[kBlk];
+  __shared__ T rNew[CPB * CD];
+  double vQ = 0.0;
+  for (int i = threadIdx.x; i < nbQ; i += kBlk) vQ += partQ[i];
+  sm[threadIdx.x] = vQ;
+  __syncthreads();
+  for (int st = kBlk / 2; st > 0; st >>= 1) {
+    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
+    __syncthreads();
+  }
+  const double pq = sm[0];
+  const double rho = *rhoIn;
+  __syncthreads();  // sm is reused for the rho partial below
+  if (blockIdx.x == 0 && threadIdx.x == 0) *rhoPrevOut = rho;
+  const T a = (T)(pq != 0.0 ? rho / pq : 0.0);
+  const int t = (int)threadIdx.x;
+  const int cl = t / CD;  // camera within the block
+  const int64_t cam = (int64_t)blockIdx.x * CPB + cl;
+  const bool live = cl < CPB && cam < ncam;
+  const int64_t i = cam * CD + (t - cl * CD);
+  T rn = T(0);
+  if (live) {
+    xBakPrev[i] = xBak[i];
+    const T xv = x[i];
+    xBak[i] = xv;
+    x[i] = xv + a * p[i];
+    rn = r[i] - a * q[i];
+    r[i] = rn;
+    rNew[t] = rn;
+  }
+  __syncthreads();
+  double local = 0.0;
+  if (live) {
+    const T* row = Binv + cam * CD * CD + (int64_t)(t - cl * CD) * CD;
+    const T* xb = rNew + cl * CD;
+    T sv = T(0);
+    for (int j = 0; j < CD; ++j) sv += row[j] * xb[j];
+    z[i] = sv;
+    local = (double)sv * (double)rn;
+  }
+  sm[threadIdx.x] = local;
+  __syncthreads();
+  for (int st = kBlk / 2; st > 0; st >>= 1) {
+    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
+}
+
 // r = v - q
 template <typename T>
 __global__ void kSub(int64_t n, const T* __restrict__ v, const T* __restrict__ q,
@@ -2033,7 +2192,11 @@ class GpuEngine final : public Engine<T> {
 
     // Partial-sum scratch: big enough for both the fixed-shape two-pass
     // reductions (kRedBlocks) and the fused B-apply+dot grid over nc_.
+    // The rotated PCG body adds two more producers: one rho partial per
+    // kUpdateXRPrecond block and one p.q partial per 64 columns.
     partCap_ = kRedBlocks > gridFor(nc_) ? kRedBlocks : gridFor(nc_);
+    if (partCap_ < precondGrid()) partCap_ = precondGrid();
+    if (partCap_ < (int)((nc_ + 63) / 64)) partCap_ = (int)((nc_ + 63) / 64);
     dPart_ = dalloc<double>(partCap_ + 8);
     dPartQ_ = dalloc<double>(partCap_);
     dFail_ = dalloc<int>(2);
@@ -2406,6 +2569,11 @@ class GpuEngine final : public Engine<T> {
     HIP_CHECK(hipMemsetAsync(dP_, 0, nc_ * sizeof(T), stream_));
     hipLaunchKernelGGL(kSetScalar, dim3(1), dim3(1), 0, stream_, slotRhoPrev(),
                        INFINITY);
+    // Rotated body: the first z = Binv r and rho partials come from here,
+    // every later one from the tail of the previous body.
+    if (pcgFuse_)
+      hipLaunchKernelGGL((kPrecondRho<T, CD>), dim3(precondGrid()), dim3(kBlk),
+                         0, stream_, ncam_, dHppInv_, dRr_, dZ_, dPart_);
     int n = 0;
     double rho = 0.0, rhoMin = INFINITY;
     bool done = false;
@@ -2677,6 +2845,10 @@ class GpuEngine final : public Engine<T> {
     sync();
     return *hScalar_;
   }
+  // No communicator and no host callback: allreduce() does nothing.
+  bool allreduceIsNoop() const {
+    return !hasComm_ && (world_ == 1 || !hostAr_);
+  }
   void allreduce(T* buf, int64_t n, ncclRedOp_t op) {
     if (n == 0 || (world_ == 1 && !hasComm_)) return;
     if (hasComm_) {
@@ -2823,11 +2995,13 @@ class GpuEngine final : public Engine<T> {
     const int g = (nWin + 3) / 4 < 8192 ? (nWin + 3) / 4 : 8192;
     return g < 1 ? 1 : g;
   }
-  // Common start of the window passes: the XP-padded copy of x, and a zeroed
-  // temp when >64-edge runs will add partials to it.
+  // Common start of the window passes: the XP-padded copy of x (unless the
+  // PCG body's kBetaPPad just wrote it), and a zeroed temp when >64-edge runs
+  // will add partials to it.
   void windowPrologue(const T* xv) {
-    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                       stream_, ncam_, xv, dXPad_);
+    if (!xPadCurrent_)
+      hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
+                         stream_, ncam_, xv, dXPad_);
     if (nLongPts_ > 0)
       hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
                          dim3(kBlk), 0, stream_, dTemp_ + (int64_t)ptLo_ * PD,
@@ -2899,8 +3073,10 @@ class GpuEngine final : public Engine<T> {
   }
 
   // out = E Cinv E^T x (local part) in one pass over the primary-sorted J
-  // with a per-workgroup LDS accumulator; out is fully overwritten.
-  void schurFusedLdsEcE(const T* xv, T* out) {
+  // with a per-workgroup LDS accumulator; out is fully overwritten.  With
+  // bApplyDot the row reduce carries on to out = HppD x - out and the x.out
+  // partials (dPartQ_), which needs nLongPts_ == 0.
+  void schurFusedLdsEcE(const T* xv, T* out, bool bApplyDot = false) {
     windowPrologue(xv);
     const size_t ldsBytes = (size_t)nc_ * sizeof(T);
     dispatchMode([&](auto impTag, auto infoTag) {
@@ -2913,6 +3089,13 @@ class GpuEngine final : public Engine<T> {
                          dInfo_, lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_,
                          (int)nc_, dLdsRows_);
     });
+    if (bApplyDot) {
+      hipLaunchKernelGGL((kLdsReduceBApplyDot<T, CD>),
+                         dim3((int)((nc_ + 63) / 64)), dim3(64 * kLdsRedWaves),
+                         0, stream_, numCU_, (int)nc_, dLdsRows_, dHppD_, xv,
+                         out, dPartQ_);
+      return;
+    }
     hipLaunchKernelGGL(kLdsRowsReduce<T>, dim3((int)((nc_ + 63) / 64)),
                        dim3(64 * kLdsRedWaves), 0, stream_, numCU_, (int)nc_,
                        dLdsRows_, out);
@@ -2955,8 +3138,9 @@ class GpuEngine final : public Engine<T> {
     }
     // 16B-aligned padded copy of x: the per-edge camera gather becomes
     // XP/VEC vector loads instead of CD divergent scalar loads.
-    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                       stream_, ncam_, xv, dXPad_);
+    if (!xPadCurrent_)
+      hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
+                         stream_, ncam_, xv, dXPad_);
     dispatchMode([&](auto, auto infoTag) {
       constexpr bool HI = decltype(infoTag)::value;
       const auto kernel = etxAtomic_ ? kSpmvEtxPkAtomic<T, CD, PD, RD, HI>
@@ -2988,6 +3172,10 @@ class GpuEngine final : public Engine<T> {
   // read pass over p,q per iteration — part of the N=8 constant term,
   // PLAN_r02 item 3).
   void pcgBody() {
+    if (pcgFuse_) {
+      pcgBodyRotated();
+      return;
+    }
     const int rhoGrid = gridFor(nc_) < kRedBlocks ? gridFor(nc_) : kRedBlocks;
     hipLaunchKernelGGL((kPrecondRho<T, CD>), dim3(rhoGrid), dim3(kBlk), 0,
                        stream_, ncam_, dHppInv_, dRr_, dZ_, dPart_);
@@ -2996,9 +3184,56 @@ class GpuEngine final : public Engine<T> {
                        slotRho(), dP_);
     schurApply(dP_, dQ_, /*withDot=*/true);
     hipLaunchKernelGGL(kUpdateXRAlpha<T>, dim3(gridFor(nc_)), dim3(kBlk), 0,
-                       stream_, nc_, dPart_, rhoGrid, dPartQ_, gridFor(nc_),
+                       stream_, nc_, dPart_, rhoGrid, dPartQ_, nPartQ_,
                        slotRhoPrev(), dP_, dQ_, dDeltaX_, dXBak_, dXBakPrev_,
                        dRr_);
+  }
+
+  // Blocks of kUpdateXRPrecond (kBlk / CD whole cameras each) = number of
+  // rho partials in the rotated body.
+  int precondGrid() const {
+    constexpr int CPB = kBlk / CD;
+    return ncam_ > 0 ? (ncam_ + CPB - 1) / CPB : 1;
+  }
+  // Does the product of the PCG body read the XP-padded copy of p?  Only the
+  // explicit separate-pass kSpmvEtx reads the unpadded vector.
+  bool pcgProductReadsPad() const {
+    return implicit_ || useFused_ || useLds_ || etxFuse_;
+  }
+  // The rotated body (default; MEGBA_NO_PCG_FUSE=1 keeps the one above).
+  // z and the rho partials of the current residual already exist: from the
+  // kPrecondRho before the loop, or from the previous body's last kernel.
+  //   A  kBetaPPad:         rho -> slotRho(), beta, p = z + beta p, dXPad_
+  //      product            (skips its own kPadX)
+  //   B  kLdsReduceBApplyDot when eligible, else reduce .. kBApplyDot
+  //   C  kUpdateXRPrecond:  alpha, rho -> slotRhoPrev(), x/xBak/xBakPrev/r,
+  //                         z = Binv r_new, next rho partials
+  void pcgBodyRotated() {
+    const int nbR = precondGrid();
+    if (pcgProductReadsPad()) {
+      constexpr int VEC = 16 / (int)sizeof(T);
+      constexpr int XP = (CD + VEC - 1) / VEC * VEC;
+      hipLaunchKernelGGL((kBetaPPad<T, CD>),
+                         dim3(gridFor((int64_t)ncam_ * XP)), dim3(kBlk), 0,
+                         stream_, ncam_, dZ_, dPart_, nbR, slotRhoPrev(),
+                         slotRho(), dP_, dXPad_);
+      xPadCurrent_ = true;
+    } else {
+      hipLaunchKernelGGL(kXpbySBeta<T>, dim3(gridFor(nc_)), dim3(kBlk), 0,
+                         stream_, nc_, dZ_, dPart_, nbR, slotRhoPrev(),
+                         slotRho(), dP_);
+    }
+    try {
+      schurApply(dP_, dQ_, /*withDot=*/true);
+    } catch (...) {
+      xPadCurrent_ = false;
+      throw;
+    }
+    xPadCurrent_ = false;
+    hipLaunchKernelGGL((kUpdateXRPrecond<T, CD>), dim3(nbR), dim3(kBlk), 0,
+                       stream_, ncam_, slotRho(), dPartQ_, nPartQ_,
+                       slotRhoPrev(), dP_, dQ_, dDeltaX_, dXBak_, dXBakPrev_,
+                       dRr_, dHppInv_, dZ_, dPart_);
   }
 
   // Capture the PCG body as a hipGraph, once.  The implicit path reads the
@@ -3079,16 +3314,25 @@ class GpuEngine final : public Engine<T> {
   // site A4 needed an additional 3*npt allreduce here).  withDot fuses the
   // x^T q dot partials into the B-apply pass (used by the PCG body).
   void schurApply(const T* xv, T* q, bool withDot = false) {
+    // Row reduce, B-apply and dot in one kernel when nothing sits between
+    // them: LDS path, no long-run finishers, no collective.
+    if (withDot && pcgFuse_ && useLds_ && !useFused_ && nLongPts_ == 0 &&
+        allreduceIsNoop()) {
+      schurFusedLdsEcE(xv, q, /*bApplyDot=*/true);
+      nPartQ_ = (int)((nc_ + 63) / 64);
+      return;
+    }
     if (useFused_) {
       schurFusedEcE(xv, q);
     } else {
       localSchurEcE(xv, q);
     }
     allreduce(q, nc_, ncclSum);
-    if (withDot)
+    if (withDot) {
       hipLaunchKernelGGL((kBApplyDot<T, CD>), dim3(gridFor(nc_)), dim3(kBlk),
                          0, stream_, ncam_, dHppD_, xv, q, dPartQ_);
-    else
+      nPartQ_ = gridFor(nc_);
+    } else
       blockMatVec<CD, 1>(ncam_, dHppD_, xv, q);
   }
 
@@ -3118,6 +3362,11 @@ class GpuEngine final : public Engine<T> {
   // the real data at the first solve (autoTuneEtx); env overrides force.
   bool etxFuse_ = getenv("MEGBA_NO_ETXFUSE") == nullptr;
   bool etxTuned_ = false;
+  // Rotated PCG body with merged vector kernels (pcgBodyRotated);
+  // MEGBA_NO_PCG_FUSE=1 keeps the seven-kernel body.
+  bool pcgFuse_ = getenv("MEGBA_NO_PCG_FUSE") == nullptr;
+  bool xPadCurrent_ = false;  // dXPad_ already holds the product's input
+  int nPartQ_ = 0;            // p.q partials the last schurApply wrote
   // LDS single-pass Schur apply (kSchurFusedLds): eligible when the camera
   // vector fits the per-workgroup LDS limit; chosen by autoTuneEtx or
   // forced with MEGBA_SCHUR_LDS.
