@@ -17,6 +17,7 @@
 #include "megba/engine.hpp"
 #include "megba/lm.hpp"
 #include "megba/problem.hpp"
+#include "megba/gpu/edge_tables.hpp"  // host-only
 
 #ifdef MEGBA_WITH_GPU
 #include "megba/gpu/gpu_engine.hpp"
@@ -480,6 +481,59 @@ PYBIND11_MODULE(_core, m) {
       .def("get_params", &PyProblem::getParams)
       .def("dump", &PyProblem::dump)
       .def("index_info", &PyProblem::indexInfo);
+
+  // Debug view of the GPU engine's host-built edge tables for one rank of a
+  // (cam_idx, pt_idx) problem; runs on the host only.
+  m.def(
+      "gpu_edge_tables",
+      [](py::array_t<int, py::array::c_style | py::array::forcecast> camIdx,
+         py::array_t<int, py::array::c_style | py::array::forcecast> ptIdx,
+         int ncam, int npt, int rank, int world, int chunkRows, int bandPts) {
+        MEGBA_CHECK(camIdx.size() == ptIdx.size(), "index array size mismatch");
+        MEGBA_CHECK(rank >= 0 && rank < world, "rank out of range");
+        MEGBA_CHECK(chunkRows >= 1, "chunk_rows must be positive");
+        BAProblemHost p;
+        p.ncam = ncam;
+        p.npt = npt;
+        p.nobs = camIdx.size();
+        p.camIdx.assign(camIdx.data(), camIdx.data() + p.nobs);
+        p.ptIdx.assign(ptIdx.data(), ptIdx.data() + p.nobs);
+        p.meas.assign((size_t)p.nobs * p.resDim, 0.0);
+        const ProblemIndex ix = buildIndex(p, world);
+        const int64_t e0 = ix.split[rank], e1 = ix.split[rank + 1];
+        const int ptLo = ix.ptSplit[rank], ptHi = ix.ptSplit[rank + 1];
+        const CamChunks c =
+            buildCamChunks(ix, e0, e1, ncam, npt, chunkRows, bandPts);
+        const RunWindows w = buildRunWindows(ix, e0, ptLo, ptHi);
+        const auto arr = [](const auto& v) {
+          using U = typename std::decay_t<decltype(v)>::value_type;
+          return py::array_t<U>((py::ssize_t)v.size(), v.data());
+        };
+        py::dict d;
+        d["e0"] = e0;
+        d["e1"] = e1;
+        d["pt_lo"] = ptLo;
+        d["pt_hi"] = ptHi;
+        // the rank's edges in primary (pt, cam)-sorted order
+        d["cam_of"] = arr(std::vector<int>(ix.camOf.begin() + e0,
+                                           ix.camOf.begin() + e1));
+        d["pt_of"] = arr(std::vector<int>(ix.ptOf.begin() + e0,
+                                          ix.ptOf.begin() + e1));
+        d["cam_pos"] = arr(c.camPos);
+        d["pt_of_cam"] = arr(c.ptOfCam);
+        d["ch_cam"] = arr(c.chCam);
+        d["ch_lo"] = arr(c.chLo);
+        d["ch_hi"] = arr(c.chHi);
+        d["win_lo"] = arr(w.winLo);
+        d["win_hi"] = arr(w.winHi);
+        d["win_flag"] = arr(w.winFlag);
+        d["flag_wins"] = arr(w.flagWins);
+        d["long_pts"] = arr(w.longPts);
+        return d;
+      },
+      py::arg("cam_idx"), py::arg("pt_idx"), py::arg("ncam"), py::arg("npt"),
+      py::arg("rank") = 0, py::arg("world") = 1, py::arg("chunk_rows") = 256,
+      py::arg("band_pts") = 0);
 
 #ifdef MEGBA_WITH_GPU
   m.attr("has_gpu_support") = true;

@@ -1,6 +1,6 @@
 // Per-edge and per-run device primitives shared by the Schur product
 // kernels (E^T x, Cinv, E w and their fused window forms) in
-// gpu_engine_impl.hpp: inline templates over register arrays taken by
+// kernels_product.hpp: inline templates over register arrays taken by
 // reference.  Their loops fix the floating-point summation order of the
 // paths that use them.
 #pragma once

@@ -1,0 +1,742 @@
+// Schur product kernels: E^T x, Cinv and E w as separate passes, their fused
+// window forms, the LDS single-pass apply and its row reduce.
+#pragma once
+
+#include "edge_ops.hpp"
+#include "gpu_common.hpp"
+
+namespace megba {
+namespace {
+
+// ---------------------------------------------------------------------------
+// Packed-J layout for the per-iteration implicit products
+// ---------------------------------------------------------------------------
+// The grad-major J layout ([k][nL], one 4/8-byte load per value) makes the
+// two matrix-free PCG kernels instruction-ISSUE-bound: ~24 scalar loads
+// per edge dominate the ~80-instruction inner loop (measured ~2x the byte
+// floor on final13682-fp32, profiles/r01_final13682_implicit_fp32.md).
+// Repacking the 24 per-edge J values into 16-byte vector groups
+// ([group][nL][VEC], VEC = 16B/sizeof(T)) turns them into NG=24/VEC
+// dwordx4 loads (6 for fp32, 12 for fp64), still fully coalesced across
+// the 64 consecutive-edge lanes.  The pack runs once per ACCEPTED LM step
+// (its cost amortizes over the ~100 PCG iterations that read it); the
+// packed buffers are single-buffered so the captured PCG graph needs no
+// pointer indirection for them.
+// (The standalone kPackJPrimary pass was folded into kAssembleEdge's
+// register writes in r2.)
+
+// Packed E^T x (implicit): kSpmvEtx's run scan over t_e = Jp^T W (Jc x)
+// from the vector-group J.  The accepted r is read through the device
+// pointer slots so a captured graph stays valid across accept-time flips.
+template <typename T, int CD, int PD, int RD, bool HASINFO>
+__global__ void kSpmvEtxPk(int64_t nL, const int* __restrict__ camOf,
+                           const int* __restrict__ ptOf,
+                           const T* __restrict__ Jpk,
+                           const T* const* __restrict__ jSlots,
+                           const T* __restrict__ info, int lossKind, T lossD2,
+                           const T* __restrict__ xPad,
+                           T* __restrict__ out) {
+  using TV = typename PackVec<T>::type;
+  constexpr int VEC = PackVec<T>::VEC;
+  constexpr int RW = RD * (RD + 1) / 2;
+  constexpr int CR = CD * RD, PR = PD * RD;
+  constexpr int NG = PackedEdge<T, CD, PD, RD, true>::NG;
+  const T* rBak = jSlots[2];
+  const int lane = threadIdx.x & 63;
+  const int64_t nWork = ((nL + kBlk - 1) / kBlk) * (int64_t)kBlk;
+  for (int64_t j0 = blockIdx.x * (int64_t)kBlk + threadIdx.x; j0 < nWork;
+       j0 += (int64_t)gridDim.x * kBlk) {
+    const bool active = j0 < nL;
+    const int64_t j = active ? j0 : nL - 1;
+    const int pt = ptOf[j];
+    T o[PD];
+    for (int k = 0; k < PD; ++k) o[k] = T(0);
+    if (active) {
+      constexpr int XP = PackedEdge<T, CD, PD, RD, true>::XP;
+      const TV* xv4 = (const TV*)(xPad + (int64_t)camOf[j] * XP);
+      TV xbuf[XP / VEC];
+#pragma unroll
+      for (int l = 0; l < XP / VEC; ++l) xbuf[l] = xv4[l];
+      TV buf[NG];
+      const TV* src = (const TV*)Jpk;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) buf[g] = src[(int64_t)g * nL + j];
+      T u[RD];
+#pragma unroll
+      for (int rr = 0; rr < RD; ++rr) {
+        T v = T(0);
+#pragma unroll
+        for (int i = 0; i < CD; ++i) {
+          const int k = i * RD + rr;
+          v += buf[k / VEC][k % VEC] * xbuf[i / VEC][i % VEC];
+        }
+        u[rr] = v;
+      }
+      if (HASINFO) {
+        T wu[RD];
+        for (int i = 0; i < RD; ++i) {
+          T v = T(0);
+          for (int k = 0; k < RD; ++k)
+            v += info[RW * j + symIdx<RD>(i, k)] * u[k];
+          wu[i] = v;
+        }
+        for (int i = 0; i < RD; ++i) u[i] = wu[i];
+      }
+      if (lossKind) {
+        T ss = T(0);
+        for (int rr = 0; rr < RD; ++rr) {
+          const T rv = rBak[(int64_t)rr * nL + j];
+          ss += rv * rv;
+        }
+        const T w = lossWeight(lossKind, lossD2, ss);
+        for (int rr = 0; rr < RD; ++rr) u[rr] *= w;
+      }
+#pragma unroll
+      for (int k = 0; k < PD; ++k) {
+        T v = T(0);
+#pragma unroll
+        for (int rr = 0; rr < RD; ++rr) {
+          const int kk = CR + k * RD + rr;
+          v += buf[kk / VEC][kk % VEC] * u[rr];
+        }
+        o[k] = v;
+      }
+    }
+    waveSegScan(pt, lane, o);
+    if (runTailTiled(pt, lane, active, j0 == nL - 1))
+      for (int k = 0; k < PD; ++k) atomicAdd(&out[PD * pt + k], o[k]);
+  }
+}
+
+// Scan-free E^T x variant (env MEGBA_ETX_ATOMIC=1): PD atomicAdds per
+// edge instead of the wave segmented scan + tail atomics.  The scan costs
+// ~16 dependent shuffle instructions per edge; the atomics serialize on
+// the ~degree-5 same-point runs.  Which wins is measured, not assumed.
+template <typename T, int CD, int PD, int RD, bool HASINFO>
+__global__ void kSpmvEtxPkAtomic(int64_t nL, const int* __restrict__ camOf,
+                                 const int* __restrict__ ptOf,
+                                 const T* __restrict__ Jpk,
+                                 const T* const* __restrict__ jSlots,
+                                 const T* __restrict__ info, int lossKind,
+                                 T lossD2, const T* __restrict__ xPad,
+                                 T* __restrict__ out) {
+  const T* rBak = jSlots[2];
+  for (int64_t j = blockIdx.x * (int64_t)kBlk + threadIdx.x; j < nL;
+       j += (int64_t)gridDim.x * kBlk) {
+    const int pt = ptOf[j];
+    using PE = PackedEdge<T, CD, PD, RD, true>;
+    typename PackVec<T>::type xbuf[PE::NX], buf[PE::NG];
+    loadXPadded<T>(xPad, camOf[j], xbuf);
+    loadGroups<T>(Jpk, nL, j, buf);
+    T t[PD];
+    packedEtx<T, CD, PD, RD, HASINFO>(buf, xbuf, j, nL, info, rBak, lossKind,
+                                      lossD2, t);
+    for (int k = 0; k < PD; ++k) atomicAdd(&out[PD * pt + k], t[k]);
+  }
+}
+
+// Packed E w over the cam-sorted [wJc(CR), Jp(PR)] groups.
+template <typename T, int CD, int PD, int RD>
+__global__ __launch_bounds__(64) void kSpmvExPk(
+    int nChunks, const int* __restrict__ chCam, const int* __restrict__ chLo,
+    const int* __restrict__ chHi, const int* __restrict__ ptOfCam,
+    const T* __restrict__ JCamPk, int64_t nL, const T* __restrict__ w,
+    T* __restrict__ out) {
+  using TV = typename PackVec<T>::type;
+  constexpr int VEC = PackVec<T>::VEC;
+  constexpr int CR = CD * RD, PR = PD * RD;
+  constexpr int NG = PackedEdge<T, CD, PD, RD, true>::NG;
+  const int chunk = blockIdx.x;
+  if (chunk >= nChunks) return;
+  const int cam = chCam[chunk];
+  T acc[CD];
+  for (int i = 0; i < CD; ++i) acc[i] = T(0);
+  const int lo = chLo[chunk], hi = chHi[chunk];
+  const TV* src = (const TV*)JCamPk;
+  // w is stored 4-padded (stride 4 elements, 16B/32B aligned) so the
+  // per-edge gather is 1 (fp32) or 2 (fp64) vector loads instead of PD
+  // scalar loads — the gather is the TA-request hot spot of this kernel.
+  constexpr int WL = (4 * (int)sizeof(T) + 15) / 16;
+  for (int j = lo + (int)threadIdx.x; j < hi; j += 64) {
+    const TV* wp4 = (const TV*)(w + (int64_t)ptOfCam[j] * 4);
+    TV wbuf[WL];
+#pragma unroll
+    for (int l = 0; l < WL; ++l) wbuf[l] = wp4[l];
+    TV buf[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) buf[g] = src[(int64_t)g * nL + j];
+    T u[RD];
+#pragma unroll
+    for (int rr = 0; rr < RD; ++rr) {
+      T v = T(0);
+#pragma unroll
+      for (int k = 0; k < PD; ++k) {
+        const int kk = CR + k * RD + rr;
+        v += buf[kk / VEC][kk % VEC] * wbuf[k / VEC][k % VEC];
+      }
+      u[rr] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < CD; ++i) {
+      T v = T(0);
+#pragma unroll
+      for (int rr = 0; rr < RD; ++rr) {
+        const int k = i * RD + rr;
+        v += buf[k / VEC][k % VEC] * u[rr];
+      }
+      acc[i] += v;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    for (int i = 0; i < CD; ++i) acc[i] += __shfl_down(acc[i], off, 64);
+  if (threadIdx.x == 0) {
+    T* oc = out + (int64_t)cam * CD;
+    for (int i = 0; i < CD; ++i) atomicAdd(&oc[i], acc[i]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Schur SpMV pieces
+// ---------------------------------------------------------------------------
+// temp[3*pt] = Hpl^T x per local point (fully local, no collective): one
+// thread per primary-order edge (coalesced Hpl vector-group reads; the
+// replicated camera vector x is L2-resident), wave segmented-scan over the
+// point runs, atomics only at run tails.  Explicit mode only; the
+// matrix-free product is kSpmvEtxPk.
+template <typename T, int CD, int PD, int RD>
+__global__ void kSpmvEtx(int64_t nL, const int* __restrict__ camOf,
+                         const int* __restrict__ ptOf,
+                         const T* __restrict__ Hpl, const T* __restrict__ x,
+                         T* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nWork = ((nL + kBlk - 1) / kBlk) * (int64_t)kBlk;
+  for (int64_t j0 = blockIdx.x * (int64_t)kBlk + threadIdx.x; j0 < nWork;
+       j0 += (int64_t)gridDim.x * kBlk) {
+    const bool active = j0 < nL;
+    const int64_t j = active ? j0 : nL - 1;
+    const int pt = ptOf[j];
+    T o[PD];
+    for (int k = 0; k < PD; ++k) o[k] = T(0);
+    if (active) {
+      const T* xc = x + (int64_t)camOf[j] * CD;
+      typename PackVec<T>::type buf[PackedEdge<T, CD, PD, RD, false>::NG];
+      loadGroups<T>(Hpl, nL, j, buf);
+      packedHplTx<T, CD, PD>(buf, [&](int i) { return xc[i]; }, o);
+    }
+    waveSegScan(pt, lane, o);
+    if (runTailTiled(pt, lane, active, j0 == nL - 1))
+      for (int k = 0; k < PD; ++k) atomicAdd(&out[PD * pt + k], o[k]);
+  }
+}
+
+// out[9*cam] += E w partials: one wave per <=256-row chunk of one camera's
+// cam-sorted rows; per-lane partials, wave-wide shuffle reduce, one
+// atomicAdd set per chunk.  Caller allreduces 9*ncam (the ONLY per-PCG-
+// iteration collective).
+template <typename T, int CD, int PD>
+__global__ __launch_bounds__(64) void kSpmvEx(
+    int nChunks, const int* __restrict__ chCam, const int* __restrict__ chLo,
+    const int* __restrict__ chHi, const int* __restrict__ ptOfCam,
+    const T* __restrict__ HplCam, int64_t nL, const T* __restrict__ w,
+    T* __restrict__ out) {
+  using TV = typename PackVec<T>::type;
+  constexpr int VEC = PackVec<T>::VEC;
+  constexpr int NGH = (CD * PD + VEC - 1) / VEC;
+  constexpr int WL = (4 * (int)sizeof(T) + 15) / 16;
+  const int chunk = blockIdx.x;
+  if (chunk >= nChunks) return;
+  const int cam = chCam[chunk];
+  T acc[CD];
+  for (int i = 0; i < CD; ++i) acc[i] = T(0);
+  const int lo = chLo[chunk], hi = chHi[chunk];
+  const TV* src = (const TV*)HplCam;
+  for (int j = lo + (int)threadIdx.x; j < hi; j += 64) {
+    const TV* wp4 = (const TV*)(w + (int64_t)ptOfCam[j] * 4);
+    TV wbuf[WL];
+#pragma unroll
+    for (int l = 0; l < WL; ++l) wbuf[l] = wp4[l];
+    TV buf[NGH];
+#pragma unroll
+    for (int g = 0; g < NGH; ++g) buf[g] = src[(int64_t)g * nL + j];
+#pragma unroll
+    for (int i = 0; i < CD; ++i) {
+      T v = T(0);
+#pragma unroll
+      for (int k = 0; k < PD; ++k) {
+        const int kk = i * PD + k;
+        v += buf[kk / VEC][kk % VEC] * wbuf[k / VEC][k % VEC];
+      }
+      acc[i] += v;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    for (int i = 0; i < CD; ++i) acc[i] += __shfl_down(acc[i], off, 64);
+  if (threadIdx.x == 0) {
+    T* oc = out + (int64_t)cam * CD;
+    for (int i = 0; i < CD; ++i) atomicAdd(&oc[i], acc[i]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Fused Schur apply:  out[CD*ncam] += E Cinv E^T x  in ONE pass.
+// ---------------------------------------------------------------------------
+// The separate-pass pipeline (kSpmvEtx -> applyCinv -> kSpmvEx) reads the
+// per-edge J/Hpl data twice per PCG iteration and gathers the 3*npt w
+// vector by point id from the cam-sorted pass — on big-fp32 problems that
+// gather fetches a full 64 B line for 12 used bytes and was measured at
+// ~2x the byte floor (profiles/r01_final13682_implicit_fp32.md).  Here the
+// edges are processed in primary (pt,cam)-sorted order in WINDOWS of <=64
+// edges aligned to point-run boundaries (host-built table), one wave per
+// window:
+//   1. each lane evaluates its edge's t_e = Jp^T W (Jc x)  (x is the
+//      replicated CD*ncam vector, L2-resident),
+//   2. a wave segmented-scan sums t_e over each point run; the run tail
+//      applies the PD x PD Cinv block: w_p = Cinv t_p,
+//   3. w_p is broadcast back to the run's lanes (tail-lane shuffle) and
+//      each lane scatters its edge's E-contribution Jc^T W (Jp w_p) with
+//      CD atomicAdds into the small L2-resident camera vector.
+// J (or Hpl) is read ONCE, w never exists in HBM, and the scan/broadcast
+// replace both the temp round-trip and the gather.  Point runs longer
+// than 64 edges (high-degree landmarks) fall back to the classic path:
+// their windows only accumulate t partials into `temp` (phase 1 flag);
+// kFusedLongW then applies Cinv for those points and kFusedLongScatter
+// finishes their E-contributions.
+// The per-edge and per-run steps (fusedLoadEdge / fusedScatter, the window
+// scan, Cinv at the tail, the tail broadcast) are in edge_ops.hpp; what is
+// left in each window kernel is its loop and its sink.
+template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
+__global__ __launch_bounds__(256) void kSchurFused(
+    int nWin, const int64_t* __restrict__ winLo,
+    const int64_t* __restrict__ winHi, const unsigned char* __restrict__ winFlag,
+    int64_t nL, const int* __restrict__ camOf, const int* __restrict__ ptOf,
+    const T* __restrict__ Hpl, const T* const* __restrict__ jSlots,
+    const T* __restrict__ info, int lossKind, T lossD2,
+    const T* __restrict__ xPad, const T* __restrict__ HllInv,
+    T* __restrict__ temp, T* __restrict__ out) {
+  constexpr int PP = PD * PD;
+  const T* Jc = IMP ? jSlots[0] : nullptr;
+  const T* Jp = IMP ? jSlots[1] : nullptr;
+  const T* rBak = IMP ? jSlots[2] : nullptr;
+  const int lane = threadIdx.x & 63;
+  for (int w = blockIdx.x * 4 + ((int)threadIdx.x >> 6); w < nWin;
+       w += (int)gridDim.x * 4) {
+    const int64_t lo = winLo[w], hi = winHi[w];
+    const bool active = lo + lane < hi;
+    const int64_t j = active ? lo + lane : hi - 1;
+    const int pt = ptOf[j];
+    T jcv[RD][CD], jpv[RD][PD], hplv[CD][PD], t[PD];
+    for (int k = 0; k < PD; ++k) t[k] = T(0);
+    if (active)
+      fusedLoadEdge<T, CD, PD, RD, IMP, HASINFO>(
+          j, nL, camOf, Hpl, Jc, Jp, info, rBak, lossKind, lossD2, xPad,
+          jcv, jpv, hplv, t);
+    waveSegScan(pt, lane, t);
+    const bool tail = runTailWindow(pt, lane, active, lo, hi);
+    if (winFlag[w]) {
+      // segment of a >64-edge run: partials only (finished by the long-run
+      // kernels)
+      if (tail)
+        for (int k = 0; k < PD; ++k) atomicAdd(&temp[PD * pt + k], t[k]);
+      continue;
+    }
+    T wv[PD];
+    for (int k = 0; k < PD; ++k) wv[k] = T(0);
+    if (tail) cinvApply<T, PD>(HllInv + (int64_t)pt * PP, t, wv);
+    tailBroadcast(tail, lane, wv);
+    if (active)
+      fusedScatter<T, CD, PD, RD, IMP, HASINFO>(
+          j, nL, camOf, info, rBak, lossKind, lossD2, jcv, jpv, hplv, wv,
+          out);
+  }
+}
+
+// Fused E^T x + Cinv over run-aligned windows (the winning half of the
+// kSchurFused experiment): each window's runs are complete, so the run
+// TAIL applies the PD x PD Cinv block to the scanned t_p and stores
+// w_p = Cinv E^T x straight into the 4-padded w vector — no temp
+// round-trip, no zeroing, no atomics, and the separate Cinv pass
+// disappears.  Long (>64-edge) runs fall back to temp partials finished
+// by kFusedLongW.  E w then proceeds from wPad as usual (the gather-side
+// alternative, a fused scatter, measured 5x worse — Experiment 1).
+template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
+__global__ __launch_bounds__(256) void kEtxCinvFused(
+    int nWin, const int64_t* __restrict__ winLo,
+    const int64_t* __restrict__ winHi, const unsigned char* __restrict__ winFlag,
+    int64_t nL, const int* __restrict__ camOf, const int* __restrict__ ptOf,
+    const T* __restrict__ Hpl, const T* const* __restrict__ jSlots,
+    const T* __restrict__ info, int lossKind, T lossD2,
+    const T* __restrict__ xPad, const T* __restrict__ HllInv,
+    T* __restrict__ temp, T* __restrict__ wPad) {
+  constexpr int PP = PD * PD;
+  const T* Jc = IMP ? jSlots[0] : nullptr;
+  const T* Jp = IMP ? jSlots[1] : nullptr;
+  const T* rBak = IMP ? jSlots[2] : nullptr;
+  const int lane = threadIdx.x & 63;
+  for (int w = blockIdx.x * 4 + ((int)threadIdx.x >> 6); w < nWin;
+       w += (int)gridDim.x * 4) {
+    const int64_t lo = winLo[w], hi = winHi[w];
+    const bool active = lo + lane < hi;
+    const int64_t j = active ? lo + lane : hi - 1;
+    const int pt = ptOf[j];
+    T jcv[RD][CD], jpv[RD][PD], hplv[CD][PD], t[PD];
+    for (int k = 0; k < PD; ++k) t[k] = T(0);
+    if (active)
+      fusedLoadEdge<T, CD, PD, RD, IMP, HASINFO>(
+          j, nL, camOf, Hpl, Jc, Jp, info, rBak, lossKind, lossD2, xPad,
+          jcv, jpv, hplv, t);
+    waveSegScan(pt, lane, t);
+    const bool tail = runTailWindow(pt, lane, active, lo, hi);
+    if (winFlag[w]) {
+      if (tail)
+        for (int k = 0; k < PD; ++k) atomicAdd(&temp[PD * pt + k], t[k]);
+      continue;
+    }
+    if (tail)
+      cinvApplyPad<T, PD>(HllInv + (int64_t)pt * PP, t,
+                          wPad + (int64_t)pt * 4);
+  }
+}
+
+// Long-run phase 2: w_p = Cinv temp_p for the listed high-degree points,
+// stored into the 4-padded w vector.
+template <typename T, int PD>
+__global__ void kFusedLongW(int nPts, const int* __restrict__ longPts,
+                            const T* __restrict__ HllInv,
+                            const T* __restrict__ temp, T* __restrict__ w,
+                            int wStride) {
+  constexpr int PP = PD * PD;
+  for (int idx = blockIdx.x * (int)blockDim.x + (int)threadIdx.x; idx < nPts;
+       idx += (int)gridDim.x * (int)blockDim.x) {
+    const int pt = longPts[idx];
+    const T* tp = temp + PD * pt;
+    T* wp = w + (int64_t)wStride * pt;
+    cinvApply<T, PD>(HllInv + (int64_t)pt * PP, tp, wp);
+  }
+}
+
+// Long-run phase 3: finish the flagged windows' E-contributions with w
+// read from the global vector.
+template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
+__global__ __launch_bounds__(256) void kFusedLongScatter(
+    int nFlag, const int* __restrict__ flagWins,
+    const int64_t* __restrict__ winLo, const int64_t* __restrict__ winHi,
+    int64_t nL, const int* __restrict__ camOf, const int* __restrict__ ptOf,
+    const T* __restrict__ Hpl, const T* const* __restrict__ jSlots,
+    const T* __restrict__ info, int lossKind, T lossD2,
+    const T* __restrict__ xPad, const T* __restrict__ w,
+    T* __restrict__ out) {
+  const T* Jc = IMP ? jSlots[0] : nullptr;
+  const T* Jp = IMP ? jSlots[1] : nullptr;
+  const T* rBak = IMP ? jSlots[2] : nullptr;
+  const int lane = threadIdx.x & 63;
+  for (int f = blockIdx.x * 4 + ((int)threadIdx.x >> 6); f < nFlag;
+       f += (int)gridDim.x * 4) {
+    const int wi = flagWins[f];
+    const int64_t lo = winLo[wi], hi = winHi[wi];
+    if (lo + lane >= hi) continue;
+    const int64_t j = lo + lane;
+    const int pt = ptOf[j];
+    T jcv[RD][CD], jpv[RD][PD], hplv[CD][PD], t[PD];
+    fusedLoadEdge<T, CD, PD, RD, IMP, HASINFO>(
+        j, nL, camOf, Hpl, Jc, Jp, info, rBak, lossKind, lossD2, xPad, jcv,
+        jpv, hplv, t);
+    T wv[PD];
+    for (int k = 0; k < PD; ++k) wv[k] = w[PD * pt + k];
+    fusedScatter<T, CD, PD, RD, IMP, HASINFO>(
+        j, nL, camOf, info, rBak, lossKind, lossD2, jcv, jpv, hplv, wv,
+        out);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Single-pass Schur apply with an LDS-resident camera accumulator
+// ---------------------------------------------------------------------------
+// kSchurFused reads J once but loses to the two-pass pipeline because its
+// scatter is CD address-divergent GLOBAL atomics per edge.  When the whole
+// camera-side output (CD*ncam values of T) fits one CU's LDS, a persistent
+// workgroup per CU keeps a private copy of it in LDS, scatters with LDS
+// atomics (native ds_add_f64 / ds_add_f32) and writes its copy out once:
+//   - workgroup b of G owns the contiguous window slice
+//     [nWin*b/G, nWin*(b+1)/G) of the run-aligned window table, its waves
+//     stride through the slice (one contiguous stream of the pt-sorted J),
+//   - per window the math is kSchurFused's (t_e, segmented scan, Cinv at the
+//     run tail, tail-mask broadcast); the implicit edge comes from the
+//     PACKED primary (vector-group loads, as kSpmvEtxPk) and stays in
+//     registers for the scatter side,
+//   - flagged windows (segments of >64-edge runs) only add their t
+//     partials to `temp`; kFusedLongW / kFusedLongScatter finish them on
+//     the global output after the flush,
+//   - the flush is plain coalesced stores to row b of rows[G][nc];
+//     kLdsRowsReduce sums the G rows in fixed order and OVERWRITES out, so
+//     the cross-workgroup sum is order-fixed and out needs no memset.
+// A workgroup with an empty slice still zeroes and flushes its row.
+template <typename T, int CD, int PD, int RD, bool IMP, bool HASINFO>
+__global__ __launch_bounds__(1024) void kSchurFusedLds(
+    int nWin, const int64_t* __restrict__ winLo,
+    const int64_t* __restrict__ winHi, const unsigned char* __restrict__ winFlag,
+    int64_t nL, const int* __restrict__ camOf, const int* __restrict__ ptOf,
+    const T* __restrict__ Hpl, const T* __restrict__ Jpk,
+    const T* const* __restrict__ jSlots, const T* __restrict__ info,
+    int lossKind, T lossD2, const T* __restrict__ xPad,
+    const T* __restrict__ HllInv, T* __restrict__ temp, int nc,
+    T* __restrict__ rows) {
+  using TV = typename PackVec<T>::type;
+  constexpr int VEC = PackVec<T>::VEC;
+  constexpr int PP = PD * PD;
+  constexpr int RW = RD * (RD + 1) / 2;
+  constexpr int CR = CD * RD, PR = PD * RD;
+  constexpr int NG = PackedEdge<T, CD, PD, RD, IMP>::NG;
+  constexpr int XP = PackedEdge<T, CD, PD, RD, IMP>::XP;
+  extern __shared__ __align__(16) unsigned char ldsRaw[];
+  T* acc = reinterpret_cast<T*>(ldsRaw);
+  for (int i = (int)threadIdx.x; i < nc; i += (int)blockDim.x) acc[i] = T(0);
+  __syncthreads();
+  const T* rBak = IMP ? jSlots[2] : nullptr;
+  const TV* src = (const TV*)(IMP ? Jpk : Hpl);
+  const int lane = threadIdx.x & 63;
+  const int nWave = (int)blockDim.x >> 6;
+  const int wBeg = (int)((int64_t)nWin * blockIdx.x / gridDim.x);
+  const int wEnd = (int)((int64_t)nWin * (blockIdx.x + 1) / gridDim.x);
+  for (int w = wBeg + ((int)threadIdx.x >> 6); w < wEnd; w += nWave) {
+    const int64_t lo = winLo[w], hi = winHi[w];
+    const bool flagged = winFlag[w] != 0;
+    const bool active = lo + lane < hi;
+    const int64_t j = active ? lo + lane : hi - 1;
+    const int pt = ptOf[j];
+    const int cam = camOf[j];
+    TV buf[NG];
+    T iw[RW];
+    T lw = T(1);
+    T t[PD];
+    for (int k = 0; k < PD; ++k) t[k] = T(0);
+    if (active) {
+      const TV* xv4 = (const TV*)(xPad + (int64_t)cam * XP);
+      TV xbuf[XP / VEC];
+#pragma unroll
+      for (int l = 0; l < XP / VEC; ++l) xbuf[l] = xv4[l];
+      // The packed groups are read once per apply, by one lane each, so they
+      // are loaded non-temporal: the intent is that the stream leaves what
+      // every apply re-reads (HllInv, camOf/ptOf, the rows) in the last-level
+      // cache.  Measured on Venice in profiles/r05_pcg_fusion.md.
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+        buf[g] = __builtin_nontemporal_load(&src[(int64_t)g * nL + j]);
+      if (IMP) {
+        T u[RD];
+#pragma unroll
+        for (int rr = 0; rr < RD; ++rr) {
+          T v = T(0);
+#pragma unroll
+          for (int i = 0; i < CD; ++i) {
+            const int k = i * RD + rr;
+            v += buf[k / VEC][k % VEC] * xbuf[i / VEC][i % VEC];
+          }
+          u[rr] = v;
+        }
+        if (HASINFO) {
+          for (int k = 0; k < RW; ++k) iw[k] = info[RW * j + k];
+          T wu[RD];
+          for (int i = 0; i < RD; ++i) {
+            T v = T(0);
+            for (int k = 0; k < RD; ++k) v += iw[symIdx<RD>(i, k)] * u[k];
+            wu[i] = v;
+          }
+          for (int i = 0; i < RD; ++i) u[i] = wu[i];
+        }
+        if (lossKind) {
+          T ss = T(0);
+          for (int rr = 0; rr < RD; ++rr) {
+            const T rv = rBak[(int64_t)rr * nL + j];
+            ss += rv * rv;
+          }
+          lw = lossWeight(lossKind, lossD2, ss);
+          for (int rr = 0; rr < RD; ++rr) u[rr] *= lw;
+        }
+#pragma unroll
+        for (int k = 0; k < PD; ++k) {
+          T v = T(0);
+#pragma unroll
+          for (int rr = 0; rr < RD; ++rr) {
+            const int kk = CR + k * RD + rr;
+            v += buf[kk / VEC][kk % VEC] * u[rr];
+          }
+          t[k] = v;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < CD; ++i) {
+          const T xi = xbuf[i / VEC][i % VEC];
+#pragma unroll
+          for (int k = 0; k < PD; ++k) {
+            const int kk = i * PD + k;
+            t[k] += buf[kk / VEC][kk % VEC] * xi;
+          }
+        }
+      }
+    }
+    // segmented inclusive scan over the window's point runs
+    for (int off = 1; off < 64; off <<= 1) {
+      const int ppt = __shfl_up(pt, off, 64);
+      const bool join = lane >= off && ppt == pt;
+      if (__ballot(join) == 0ull) break;
+      T a[PD];
+      for (int k = 0; k < PD; ++k) a[k] = __shfl_up(t[k], off, 64);
+      if (join)
+        for (int k = 0; k < PD; ++k) t[k] += a[k];
+    }
+    const int nextPt = __shfl_down(pt, 1, 64);
+    const bool tail = active && (lo + lane == hi - 1 || nextPt != pt);
+    if (flagged) {
+      if (tail)
+        for (int k = 0; k < PD; ++k) atomicAdd(&temp[PD * pt + k], t[k]);
+      continue;
+    }
+    T wv[PD];
+    for (int k = 0; k < PD; ++k) wv[k] = T(0);
+    if (tail) {
+      const T* inv = HllInv + (int64_t)pt * PP;
+      for (int i = 0; i < PD; ++i) {
+        T v = T(0);
+        for (int k = 0; k < PD; ++k) v += inv[i * PD + k] * t[k];
+        wv[i] = v;
+      }
+    }
+    // broadcast w_p from the run tail back to every lane of the run
+    const unsigned long long tails = __ballot(tail);
+    const unsigned long long from = tails >> lane;
+    const int tl = from ? lane + __ffsll((long long)from) - 1 : lane;
+    for (int k = 0; k < PD; ++k) wv[k] = __shfl(wv[k], tl, 64);
+    if (!active) continue;
+    T* oc = acc + cam * CD;
+    if (IMP) {
+      T u[RD];
+#pragma unroll
+      for (int rr = 0; rr < RD; ++rr) {
+        T v = T(0);
+#pragma unroll
+        for (int k = 0; k < PD; ++k) {
+          const int kk = CR + k * RD + rr;
+          v += buf[kk / VEC][kk % VEC] * wv[k];
+        }
+        u[rr] = v;
+      }
+      if (HASINFO) {
+        T wu[RD];
+        for (int i = 0; i < RD; ++i) {
+          T v = T(0);
+          for (int k = 0; k < RD; ++k) v += iw[symIdx<RD>(i, k)] * u[k];
+          wu[i] = v;
+        }
+        for (int i = 0; i < RD; ++i) u[i] = wu[i];
+      }
+      if (lossKind)
+        for (int rr = 0; rr < RD; ++rr) u[rr] *= lw;
+#pragma unroll
+      for (int i = 0; i < CD; ++i) {
+        T v = T(0);
+#pragma unroll
+        for (int rr = 0; rr < RD; ++rr) {
+          const int k = i * RD + rr;
+          v += buf[k / VEC][k % VEC] * u[rr];
+        }
+        atomicAdd(&oc[i], v);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < CD; ++i) {
+        T v = T(0);
+#pragma unroll
+        for (int k = 0; k < PD; ++k) {
+          const int kk = i * PD + k;
+          v += buf[kk / VEC][kk % VEC] * wv[k];
+        }
+        atomicAdd(&oc[i], v);
+      }
+    }
+  }
+  __syncthreads();
+  T* row = rows + (int64_t)blockIdx.x * nc;
+  for (int i = (int)threadIdx.x; i < nc; i += (int)blockDim.x) row[i] = acc[i];
+}
+
+// out[i] = sum over the G workgroup rows, in fixed order (overwrites out).
+// 64 columns per block; each of the block's kLdsRedWaves waves sums a
+// contiguous share of the G rows, and wave 0 combines the shares through
+// LDS in fixed order.
+constexpr int kLdsRedWaves = 16;
+template <typename T>
+__global__ __launch_bounds__(64 * kLdsRedWaves) void kLdsRowsReduce(
+    int G, int nc, const T* __restrict__ rows, T* __restrict__ out) {
+  __shared__ T sm[kLdsRedWaves][64];
+  const int lane = threadIdx.x & 63;
+  const int col = blockIdx.x * 64 + lane;
+  const int q = (int)threadIdx.x >> 6;
+  const int g0 = (int)((int64_t)G * q / kLdsRedWaves);
+  const int g1 = (int)((int64_t)G * (q + 1) / kLdsRedWaves);
+  T s = T(0);
+  if (col < nc) {
+#pragma unroll 8
+    for (int g = g0; g < g1; ++g) s += rows[(int64_t)g * nc + col];
+  }
+  sm[q][lane] = s;
+  __syncthreads();
+  if (q == 0 && col < nc) {
+    T v = sm[0][lane];
+    for (int k = 1; k < kLdsRedWaves; ++k) v += sm[k][lane];
+    out[col] = v;
+  }
+}
+
+// Block-diagonal matvec, one thread per output row.
+// MODE 0: y = A x;  MODE 1: y = A x - y  (the reference's rw=1,dw=-1 gemv).
+template <typename T, int D, int MODE>
+__global__ void kBlockDiagMatVec(int nBlk, const T* __restrict__ A,
+                                 const T* __restrict__ x, T* __restrict__ y) {
+  for (int64_t idx = blockIdx.x * (int64_t)kBlk + threadIdx.x;
+       idx < (int64_t)nBlk * D; idx += (int64_t)gridDim.x * kBlk) {
+    const int64_t b = idx / D;
+    const int rrow = (int)(idx % D);
+    const T* row = A + b * D * D + (int64_t)rrow * D;
+    const T* xb = x + b * D;
+    T s = T(0);
+    for (int j = 0; j < D; ++j) s += row[j] * xb[j];
+    y[idx] = (MODE == 0) ? s : s - y[idx];
+  }
+}
+
+// Cinv apply writing the 4-padded w layout read by kSpmvExPk: one thread
+// per point, whole padded slot written as 16/32-byte vector stores.
+template <typename T, int PD>
+__global__ void kCinvPad(int nBlk, const T* __restrict__ A,
+                         const T* __restrict__ x, T* __restrict__ yPad) {
+  for (int64_t b = blockIdx.x * (int64_t)kBlk + threadIdx.x; b < nBlk;
+       b += (int64_t)gridDim.x * kBlk)
+    cinvApplyPad<T, PD>(A + b * PD * PD, x + b * PD, yPad + b * 4);
+}
+
+// Pad the CD-stride camera vector to a 16B-aligned XP stride (one vector
+// store per camera) so the E^T x per-edge gather is XP/VEC vector loads
+// instead of CD divergent scalar loads.
+template <typename T, int CD>
+__global__ void kPadX(int ncam, const T* __restrict__ x,
+                      T* __restrict__ xPad) {
+  using TV = typename PackVec<T>::type;
+  constexpr int VEC = PackVec<T>::VEC;
+  constexpr int XP = (CD + VEC - 1) / VEC * VEC;
+  for (int64_t c = blockIdx.x * (int64_t)kBlk + threadIdx.x; c < ncam;
+       c += (int64_t)gridDim.x * kBlk) {
+    const T* xc = x + c * CD;
+    TV* o = (TV*)(xPad + c * XP);
+    for (int l = 0; l < XP / VEC; ++l) {
+      TV v;
+      for (int q = 0; q < VEC; ++q) {
+        const int k = l * VEC + q;
+        v[q] = k < CD ? xc[k] : T(0);
+      }
+      o[l] = v;
+    }
+  }
+}
+
+}  // namespace
+}  // namespace megba

@@ -1,0 +1,60 @@
+// MEGBA_* environment knobs of the GPU engine, read once at engine
+// construction (GpuKnobs::fromEnv) and immutable afterwards: the resolved
+// PCG plan and the captured graph depend on them.
+#pragma once
+
+#include <cstdint>
+#include <cstdlib>
+#include <optional>
+
+namespace megba {
+
+struct GpuKnobs {
+  // boolean knobs: presence of the variable means on
+  bool mfma = false;         // MEGBA_MFMA: MFMA camera assembly (fp64 BAL)
+  bool fused = false;        // MEGBA_FUSED: one-pass kSchurFused product
+  bool fwdVS = false;        // MEGBA_FWD_VS: value-share forward (BAL)
+  bool etxAtomic = false;    // MEGBA_ETX_ATOMIC: scan-free E^T x
+  bool etxFuse = false;      // MEGBA_ETXFUSE: force the fused window kernel
+  bool noEtxFuse = false;    // MEGBA_NO_ETXFUSE: force the separate passes
+  bool schurLds = false;     // MEGBA_SCHUR_LDS: force the LDS apply if eligible
+  bool noSchurLds = false;   // MEGBA_NO_SCHUR_LDS: take the LDS apply out
+  bool noPcgFuse = false;    // MEGBA_NO_PCG_FUSE: seven-kernel PCG body
+  bool noGraph = false;      // MEGBA_NO_GRAPH: no hipGraph capture
+  bool forceRccl = false;    // MEGBA_FORCE_RCCL: world-1 RCCL communicator
+  bool tuneVerbose = false;  // MEGBA_TUNE_VERBOSE: report the Schur path
+  // numeric knobs: unset = engine default
+  std::optional<int64_t> schurLdsMaxBytes;  // MEGBA_SCHUR_LDS_MAX_BYTES (atoll)
+  std::optional<int> schurLdsThreads;       // MEGBA_SCHUR_LDS_THREADS (atoi)
+  std::optional<int> chunk;                 // MEGBA_CHUNK (atoi)
+  std::optional<int> band;                  // MEGBA_BAND (atoi)
+
+  static GpuKnobs fromEnv() {
+    const auto on = [](const char* name) { return getenv(name) != nullptr; };
+    const auto num = [](const char* name) -> std::optional<int> {
+      const char* v = getenv(name);
+      return v ? std::optional<int>(std::atoi(v)) : std::nullopt;
+    };
+    GpuKnobs k;
+    k.mfma = on("MEGBA_MFMA");
+    k.fused = on("MEGBA_FUSED");
+    k.fwdVS = on("MEGBA_FWD_VS");
+    k.etxAtomic = on("MEGBA_ETX_ATOMIC");
+    k.etxFuse = on("MEGBA_ETXFUSE");
+    k.noEtxFuse = on("MEGBA_NO_ETXFUSE");
+    k.schurLds = on("MEGBA_SCHUR_LDS");
+    k.noSchurLds = on("MEGBA_NO_SCHUR_LDS");
+    k.noPcgFuse = on("MEGBA_NO_PCG_FUSE");
+    k.noGraph = on("MEGBA_NO_GRAPH");
+    k.forceRccl = on("MEGBA_FORCE_RCCL");
+    k.tuneVerbose = on("MEGBA_TUNE_VERBOSE");
+    if (const char* v = getenv("MEGBA_SCHUR_LDS_MAX_BYTES"))
+      k.schurLdsMaxBytes = std::atoll(v);
+    k.schurLdsThreads = num("MEGBA_SCHUR_LDS_THREADS");
+    k.chunk = num("MEGBA_CHUNK");
+    k.band = num("MEGBA_BAND");
+    return k;
+  }
+};
+
+}  // namespace megba
