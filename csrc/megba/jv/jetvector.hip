@@ -1,5 +1,7 @@
-// JetVector elementwise + geometry ops: HIP kernels (gfx950) and the CPU
-// (OpenMP) backend, generated from one template over operand kinds.
+// JetVector elementwise + geometry ops.  Each op's arithmetic is written once,
+// as a per-item body usable on host and device; forEachItem() runs a body
+// over all items as one grid-stride HIP kernel (gfx950) or as an OpenMP loop.
+// The bodies are templates over the op and the operand kinds.
 // Reference anchor: src/operator/jet_vector_math_impl.cu (39 hand-written
 // kernels) and src/operator/jet_vector_math_impl.cpp (host backend).
 #include <hip/hip_runtime.h>
@@ -7,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "../jet.hpp"  // MEGBA_HD
@@ -103,8 +106,116 @@ std::shared_ptr<DeviceBuf<T>> makeBuf(int64_t n, bool onGpu) {
   return b;
 }
 
+// Host memory <-> a JetVector's backend memory.
+template <typename T>
+void copyIn(bool onGpu, T* dst, const T* host, int64_t count) {
+  if (onGpu)
+    JV_HIP_CHECK(hipMemcpy(dst, host, count * sizeof(T), hipMemcpyHostToDevice));
+  else
+    std::memcpy(dst, host, count * sizeof(T));
+}
+template <typename T>
+void copyOut(bool onGpu, T* host, const T* src, int64_t count) {
+  if (onGpu)
+    JV_HIP_CHECK(hipMemcpy(host, src, count * sizeof(T), hipMemcpyDeviceToHost));
+  else
+    std::memcpy(host, src, count * sizeof(T));
+}
+
+// Dense output shaped like `ref`.
+template <typename T>
+JetVec<T> denseLike(const JetVec<T>& ref) {
+  JetVec<T> out;
+  out.nItem = ref.nItem;
+  out.N = ref.N;
+  out.onGpu = ref.onGpu;
+  out.value = makeBuf<T>(out.nItem, out.onGpu);
+  out.grad = makeBuf<T>((int64_t)out.N * out.nItem, out.onGpu);
+  return out;
+}
+
+// Dense output of a binary op, after checking that the operands agree.
+template <typename T>
+JetVec<T> denseLike(const JetVec<T>& a, const JetVec<T>& b) {
+  const JetVec<T>& ref = a.isScalar ? b : a;
+  MEGBA_CHECK(!ref.isScalar, "need at least one vector operand");
+  if (!a.isScalar && !b.isScalar) {
+    MEGBA_CHECK(a.nItem == b.nItem, "JetVector item-count mismatch");
+    MEGBA_CHECK(a.N == b.N, "JetVector gradient-width mismatch");
+    MEGBA_CHECK(a.onGpu == b.onGpu, "JetVector device mismatch");
+  }
+  return denseLike(ref);
+}
+
+// ---------------------------------------------------------------------------
+// Launcher: body(i) for every item i, on the GPU or the CPU.
+// ---------------------------------------------------------------------------
+template <typename Body>
+__global__ void kForEach(int64_t n, Body body) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    body(i);
+}
+
+inline int jvGrid(int64_t n) {
+  int64_t g = (n + 255) / 256;
+  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+// Body is a trivially copyable functor; it travels in the kernel arguments.
+template <typename Body>
+void forEachItem(bool onGpu, int64_t n, Body body) {
+  if (onGpu) {
+    hipLaunchKernelGGL(kForEach<Body>, dim3(jvGrid(n)), dim3(256), 0, 0, n,
+                       body);
+    JV_HIP_CHECK(hipGetLastError());
+  } else {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) body(i);
+  }
+}
+
+// f(tag) with a runtime enum value as an integral_constant tag.
+template <typename F>
+decltype(auto) dispatchOp(JvOp op, F&& f) {
+  switch (op) {
+    case JvOp::Add: return f(std::integral_constant<JvOp, JvOp::Add>{});
+    case JvOp::Sub: return f(std::integral_constant<JvOp, JvOp::Sub>{});
+    case JvOp::Mul: return f(std::integral_constant<JvOp, JvOp::Mul>{});
+    default: return f(std::integral_constant<JvOp, JvOp::Div>{});
+  }
+}
+template <typename F>
+decltype(auto) dispatchUnary(JvUnary op, F&& f) {
+  switch (op) {
+    case JvUnary::Neg: return f(std::integral_constant<JvUnary, JvUnary::Neg>{});
+    case JvUnary::Abs: return f(std::integral_constant<JvUnary, JvUnary::Abs>{});
+    case JvUnary::Sin: return f(std::integral_constant<JvUnary, JvUnary::Sin>{});
+    case JvUnary::Cos: return f(std::integral_constant<JvUnary, JvUnary::Cos>{});
+    default: return f(std::integral_constant<JvUnary, JvUnary::Sqrt>{});
+  }
+}
+template <typename F>
+decltype(auto) dispatchKind(JvKind k, F&& f) {
+  switch (k) {
+    case JvKind::DENSE: return f(std::integral_constant<JvKind, JvKind::DENSE>{});
+    case JvKind::JPV: return f(std::integral_constant<JvKind, JvKind::JPV>{});
+    default: return f(std::integral_constant<JvKind, JvKind::SCALAR>{});
+  }
+}
+// f(kindTag) for the kind of a vector operand (DENSE or JPV).
+template <typename T, typename F>
+void dispatchVectorKind(const JetVec<T>& a, F&& f) {
+  dispatchKind(a.kind(), [&](auto k) {
+    if constexpr (decltype(k)::value != JvKind::SCALAR) f(k);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// Per-item bodies
+// ---------------------------------------------------------------------------
 // Operand access generic over kind, usable on host and device.
-template <typename T, int K>  // 0=DENSE 1=JPV 2=SCALAR
+template <typename T, JvKind K>
 struct Operand {
   const T* value;
   const T* grad;
@@ -112,111 +223,16 @@ struct Operand {
   int gradPos;
   int64_t n;
   MEGBA_HD inline T val(int64_t i) const {
-    return K == 2 ? scalar : value[i];
+    return K == JvKind::SCALAR ? scalar : value[i];
   }
   MEGBA_HD inline T der(int g, int64_t i) const {
-    if (K == 0) return grad[(int64_t)g * n + i];
-    if (K == 1) return g == gradPos ? T(1) : T(0);
+    if (K == JvKind::DENSE) return grad[(int64_t)g * n + i];
+    if (K == JvKind::JPV) return g == gradPos ? T(1) : T(0);
     return T(0);
   }
 };
 
-template <typename T, int OP, int KA, int KB>
-__global__ void kJvBinary(Operand<T, KA> a, Operand<T, KB> b, int64_t n, int N,
-                          T* ov, T* og) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const T av = a.val(i), bv = b.val(i);
-    T v;
-    if (OP == 0) v = av + bv;
-    if (OP == 1) v = av - bv;
-    if (OP == 2) v = av * bv;
-    if (OP == 3) v = av / bv;
-    ov[i] = v;
-    for (int g = 0; g < N; ++g) {
-      const T ag = a.der(g, i), bg = b.der(g, i);
-      T d;
-      if (OP == 0) d = ag + bg;
-      if (OP == 1) d = ag - bg;
-      if (OP == 2) d = ag * bv + av * bg;
-      if (OP == 3) d = (ag - v * bg) / bv;
-      og[(int64_t)g * n + i] = d;
-    }
-  }
-}
-
-template <typename T, int OP>
-__global__ void kJvUnary(const T* av, int64_t n, int N, const T* ag_, int agPos,
-                         int agKind, T* ov, T* og) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const T v = av[i];
-    T outv, scale;  // d out = scale * d in  (except Neg/Abs sign logic)
-    if (OP == 0) { outv = -v; scale = T(-1); }
-    if (OP == 1) { outv = v < T(0) ? -v : v; scale = v < T(0) ? T(-1) : T(1); }
-    if (OP == 2) { outv = ::sin(v); scale = ::cos(v); }
-    if (OP == 3) { outv = ::cos(v); scale = -::sin(v); }
-    if (OP == 4) { outv = ::sqrt(v); scale = T(0.5) / outv; }
-    ov[i] = outv;
-    for (int g = 0; g < N; ++g) {
-      T ing;
-      if (agKind == 0) ing = ag_[(int64_t)g * n + i];
-      else if (agKind == 1) ing = g == agPos ? T(1) : T(0);
-      else ing = T(0);
-      og[(int64_t)g * n + i] = scale * ing;
-    }
-  }
-}
-
-// ---- CPU versions ----
-template <typename T, int OP, int KA, int KB>
-void cpuJvBinary(Operand<T, KA> a, Operand<T, KB> b, int64_t n, int N, T* ov,
-                 T* og) {
-#pragma omp parallel for schedule(static)
-  for (int64_t i = 0; i < n; ++i) {
-    const T av = a.val(i), bv = b.val(i);
-    T v{};
-    if (OP == 0) v = av + bv;
-    if (OP == 1) v = av - bv;
-    if (OP == 2) v = av * bv;
-    if (OP == 3) v = av / bv;
-    ov[i] = v;
-    for (int g = 0; g < N; ++g) {
-      const T ag = a.der(g, i), bg = b.der(g, i);
-      T d{};
-      if (OP == 0) d = ag + bg;
-      if (OP == 1) d = ag - bg;
-      if (OP == 2) d = ag * bv + av * bg;
-      if (OP == 3) d = (ag - v * bg) / bv;
-      og[(int64_t)g * n + i] = d;
-    }
-  }
-}
-
-template <typename T, int OP>
-void cpuJvUnary(const T* av, int64_t n, int N, const T* ag_, int agPos,
-                int agKind, T* ov, T* og) {
-#pragma omp parallel for schedule(static)
-  for (int64_t i = 0; i < n; ++i) {
-    const T v = av[i];
-    T outv{}, scale{};
-    if (OP == 0) { outv = -v; scale = T(-1); }
-    if (OP == 1) { outv = v < T(0) ? -v : v; scale = v < T(0) ? T(-1) : T(1); }
-    if (OP == 2) { outv = std::sin(v); scale = std::cos(v); }
-    if (OP == 3) { outv = std::cos(v); scale = -std::sin(v); }
-    if (OP == 4) { outv = std::sqrt(v); scale = T(0.5) / outv; }
-    ov[i] = outv;
-    for (int g = 0; g < N; ++g) {
-      T ing;
-      if (agKind == 0) ing = ag_[(int64_t)g * n + i];
-      else if (agKind == 1) ing = g == agPos ? T(1) : T(0);
-      else ing = T(0);
-      og[(int64_t)g * n + i] = scale * ing;
-    }
-  }
-}
-
-template <typename T, int K>
+template <typename T, JvKind K>
 Operand<T, K> makeOperand(const JetVec<T>& a) {
   Operand<T, K> o;
   o.value = a.value ? a.value->ptr : nullptr;
@@ -227,40 +243,138 @@ Operand<T, K> makeOperand(const JetVec<T>& a) {
   return o;
 }
 
-inline int jvGrid(int64_t n) {
-  int64_t g = (n + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+template <JvOp OP, typename T>
+MEGBA_HD inline T binaryValue(T av, T bv) {
+  if (OP == JvOp::Add) return av + bv;
+  if (OP == JvOp::Sub) return av - bv;
+  if (OP == JvOp::Mul) return av * bv;
+  return av / bv;
 }
 
-template <typename T, int OP, int KA, int KB>
-void runBinary(const JetVec<T>& a, const JetVec<T>& b, JetVec<T>& out) {
-  auto oa = makeOperand<T, KA>(a);
-  auto ob = makeOperand<T, KB>(b);
-  if (out.onGpu) {
-    hipLaunchKernelGGL((kJvBinary<T, OP, KA, KB>), dim3(jvGrid(out.nItem)),
-                       dim3(256), 0, 0, oa, ob, out.nItem, out.N,
-                       out.value->ptr, out.grad->ptr);
-    JV_HIP_CHECK(hipGetLastError());
-  } else {
-    cpuJvBinary<T, OP, KA, KB>(oa, ob, out.nItem, out.N, out.value->ptr,
-                               out.grad->ptr);
+template <typename T, JvOp OP, JvKind KA, JvKind KB>
+struct BinaryItem {
+  Operand<T, KA> a;
+  Operand<T, KB> b;
+  int64_t n;
+  int N;
+  T* ov;
+  T* og;
+  MEGBA_HD void operator()(int64_t i) const {
+    const T av = a.val(i), bv = b.val(i);
+    const T v = binaryValue<OP>(av, bv);
+    ov[i] = v;
+    for (int g = 0; g < N; ++g) {
+      const T ag = a.der(g, i), bg = b.der(g, i);
+      T d;
+      if (OP == JvOp::Add) d = ag + bg;
+      if (OP == JvOp::Sub) d = ag - bg;
+      if (OP == JvOp::Mul) d = ag * bv + av * bg;
+      if (OP == JvOp::Div) d = (ag - v * bg) / bv;
+      og[(int64_t)g * n + i] = d;
+    }
   }
-}
+};
 
-template <typename T, int OP>
-void dispatchBinary(const JetVec<T>& a, const JetVec<T>& b, JetVec<T>& out) {
-  const int ka = (int)a.kind(), kb = (int)b.kind();
-  // JvKind: DENSE=0, JPV=1, SCALAR=2 (enum order)
-  if (ka == 0 && kb == 0) runBinary<T, OP, 0, 0>(a, b, out);
-  else if (ka == 0 && kb == 1) runBinary<T, OP, 0, 1>(a, b, out);
-  else if (ka == 0 && kb == 2) runBinary<T, OP, 0, 2>(a, b, out);
-  else if (ka == 1 && kb == 0) runBinary<T, OP, 1, 0>(a, b, out);
-  else if (ka == 1 && kb == 1) runBinary<T, OP, 1, 1>(a, b, out);
-  else if (ka == 1 && kb == 2) runBinary<T, OP, 1, 2>(a, b, out);
-  else if (ka == 2 && kb == 0) runBinary<T, OP, 2, 0>(a, b, out);
-  else if (ka == 2 && kb == 1) runBinary<T, OP, 2, 1>(a, b, out);
-  else MEGBA_CHECK(false, "scalar op scalar is not a JetVector op");
-}
+template <typename T, JvUnary OP, JvKind K>
+struct UnaryItem {
+  Operand<T, K> a;
+  int64_t n;
+  int N;
+  T* ov;
+  T* og;
+  MEGBA_HD void operator()(int64_t i) const {
+    const T v = a.val(i);
+    T outv, scale;  // d out = scale * d in
+    if (OP == JvUnary::Neg) { outv = -v; scale = T(-1); }
+    if (OP == JvUnary::Abs) { outv = v < T(0) ? -v : v; scale = v < T(0) ? T(-1) : T(1); }
+    if (OP == JvUnary::Sin) { outv = std::sin(v); scale = std::cos(v); }
+    if (OP == JvUnary::Cos) { outv = std::cos(v); scale = -std::sin(v); }
+    if (OP == JvUnary::Sqrt) { outv = std::sqrt(v); scale = T(0.5) / outv; }
+    ov[i] = outv;
+    for (int g = 0; g < N; ++g) og[(int64_t)g * n + i] = scale * a.der(g, i);
+  }
+};
+
+// wrap = theta - 2*pi*floor((theta + pi) / (2*pi)), in [-pi, pi);
+// d wrap / d theta = 1.
+template <typename T, JvKind K>
+struct NormalizeAngleItem {
+  Operand<T, K> a;
+  int64_t n;
+  int N;
+  T* ov;
+  T* og;
+  MEGBA_HD void operator()(int64_t i) const {
+    // No FMA: the wrapped value has the same bits on both backends.
+#pragma clang fp contract(off)
+    const T twoPi = T(6.283185307179586476925286766559);
+    const T v = a.val(i);
+    ov[i] = v - twoPi * (T)std::floor(((double)v + 3.14159265358979323846) /
+                                      (double)twoPi);
+    for (int g = 0; g < N; ++g) og[(int64_t)g * n + i] = a.der(g, i);
+  }
+};
+
+// Rotation matrix -> unit quaternion [w,x,y,z] with gradients: per-item
+// Shepperd branch b on the largest of {trace, R00, R11, R22} (the reference's
+// RotationToQuaternion kernel, quaternion.cu:102-199, used a static device
+// function-pointer table; here one parameterised branch).  q[b] is the major
+// component sqrt(t)/2; the other three are (R[p] + sign*R[m]) / (2 sqrt(t)).
+// The pointer tables travel by value (208 bytes).
+template <typename T>
+struct Rot2QuatItem {
+  const T* rv[9];
+  const T* rg[9];
+  T* qv[4];
+  T* qg[4];
+  int64_t n;
+  int N;
+  MEGBA_HD void operator()(int64_t i) const {
+    // No FMA: the minor components' gradients are differences that cancel
+    // (to exactly 0 where q does not depend on the parameter); fused and
+    // unfused products leave different residues there, so with contraction
+    // the GPU gradient would not match the CPU's to any relative bound.
+#pragma clang fp contract(off)
+    // t = 1 + sg . (R00, R11, R22)
+    const T sg[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
+    // per branch, the three minor components as {component, p, m, sign}
+    const int oth[4][3][4] = {
+        {{1, 7, 5, -1}, {2, 2, 6, -1}, {3, 3, 1, -1}},
+        {{0, 7, 5, -1}, {2, 3, 1, +1}, {3, 2, 6, +1}},
+        {{0, 2, 6, -1}, {1, 3, 1, +1}, {3, 7, 5, +1}},
+        {{0, 3, 1, -1}, {1, 2, 6, +1}, {2, 7, 5, +1}}};
+    T v[9], q[4];
+    for (int k = 0; k < 9; ++k) v[k] = rv[k][i];
+    const T tr = v[0] + v[4] + v[8];
+    int b = 0;
+    T best = tr;
+    if (v[0] > best) { b = 1; best = v[0]; }
+    if (v[4] > best) { b = 2; best = v[4]; }
+    if (v[8] > best) { b = 3; }
+    const T t = T(1) + sg[b][0] * v[0] + sg[b][1] * v[4] + sg[b][2] * v[8];
+    const T s = std::sqrt(t);
+    const T inv2s = T(0.5) / s;
+    q[b] = s * T(0.5);
+    T comp[3];
+    for (int k = 0; k < 3; ++k) {
+      comp[k] = (v[oth[b][k][1]] + T(oth[b][k][3]) * v[oth[b][k][2]]) * inv2s;
+      q[oth[b][k][0]] = comp[k];
+    }
+    for (int k = 0; k < 4; ++k) qv[k][i] = q[k];
+    for (int g = 0; g < N; ++g) {
+      const T dt = sg[b][0] * rg[0][(int64_t)g * n + i] +
+                   sg[b][1] * rg[4][(int64_t)g * n + i] +
+                   sg[b][2] * rg[8][(int64_t)g * n + i];
+      const T ds = dt * inv2s;
+      qg[b][(int64_t)g * n + i] = ds * T(0.5);
+      for (int k = 0; k < 3; ++k) {
+        const T dn = rg[oth[b][k][1]][(int64_t)g * n + i] +
+                     T(oth[b][k][3]) * rg[oth[b][k][2]][(int64_t)g * n + i];
+        qg[oth[b][k][0]][(int64_t)g * n + i] = dn * inv2s - comp[k] * ds / s;
+      }
+    }
+  }
+};
 
 }  // namespace
 
@@ -273,18 +387,10 @@ JetVec<T> jvFromHost(const T* value, const T* grad, int64_t nItem, int N,
   v.gradPos = gradPos;
   v.onGpu = onGpu;
   v.value = makeBuf<T>(nItem, onGpu);
-  if (onGpu)
-    JV_HIP_CHECK(hipMemcpy(v.value->ptr, value, nItem * sizeof(T),
-                           hipMemcpyHostToDevice));
-  else
-    std::memcpy(v.value->ptr, value, nItem * sizeof(T));
+  copyIn(onGpu, v.value->ptr, value, nItem);
   if (grad != nullptr && gradPos < 0) {
     v.grad = makeBuf<T>((int64_t)N * nItem, onGpu);
-    if (onGpu)
-      JV_HIP_CHECK(hipMemcpy(v.grad->ptr, grad, (int64_t)N * nItem * sizeof(T),
-                             hipMemcpyHostToDevice));
-    else
-      std::memcpy(v.grad->ptr, grad, (int64_t)N * nItem * sizeof(T));
+    copyIn(onGpu, v.grad->ptr, grad, (int64_t)N * nItem);
   }
   return v;
 }
@@ -301,19 +407,10 @@ JetVec<T> jvScalar(T s, int N) {
 template <typename T>
 void jvToHost(const JetVec<T>& a, T* value, T* grad) {
   MEGBA_CHECK(!a.isScalar, "cannot download a scalar JetVector");
-  if (a.onGpu)
-    JV_HIP_CHECK(hipMemcpy(value, a.value->ptr, a.nItem * sizeof(T),
-                           hipMemcpyDeviceToHost));
-  else
-    std::memcpy(value, a.value->ptr, a.nItem * sizeof(T));
+  copyOut(a.onGpu, value, a.value->ptr, a.nItem);
   if (!grad) return;
   if (a.grad) {
-    if (a.onGpu)
-      JV_HIP_CHECK(hipMemcpy(grad, a.grad->ptr,
-                             (int64_t)a.N * a.nItem * sizeof(T),
-                             hipMemcpyDeviceToHost));
-    else
-      std::memcpy(grad, a.grad->ptr, (int64_t)a.N * a.nItem * sizeof(T));
+    copyOut(a.onGpu, grad, a.grad->ptr, (int64_t)a.N * a.nItem);
   } else {
     for (int g = 0; g < a.N; ++g)
       for (int64_t i = 0; i < a.nItem; ++i)
@@ -322,73 +419,48 @@ void jvToHost(const JetVec<T>& a, T* value, T* grad) {
 }
 
 template <typename T>
-static JetVec<T> denseLike(const JetVec<T>& a, const JetVec<T>& b) {
-  const JetVec<T>& ref = a.isScalar ? b : a;
-  MEGBA_CHECK(!ref.isScalar, "need at least one vector operand");
-  if (!a.isScalar && !b.isScalar) {
-    MEGBA_CHECK(a.nItem == b.nItem, "JetVector item-count mismatch");
-    MEGBA_CHECK(a.N == b.N, "JetVector gradient-width mismatch");
-    MEGBA_CHECK(a.onGpu == b.onGpu, "JetVector device mismatch");
-  }
-  JetVec<T> out;
-  out.nItem = ref.nItem;
-  out.N = ref.N;
-  out.onGpu = ref.onGpu;
-  out.value = makeBuf<T>(out.nItem, out.onGpu);
-  out.grad = makeBuf<T>((int64_t)out.N * out.nItem, out.onGpu);
-  return out;
-}
-
-template <typename T>
 JetVec<T> jvBinary(JvOp op, const JetVec<T>& a, const JetVec<T>& b) {
   if (a.isScalar && b.isScalar) {
     // Pure-scalar op: host arithmetic, scalar result (the reference's
     // PURE_SCALAR_OP dispatch, src/operator/jet_vector.cpp).
     MEGBA_CHECK(a.N == b.N, "JetVector gradient-width mismatch");
-    T r = T(0);
-    switch (op) {
-      case JvOp::Add: r = a.scalarVal + b.scalarVal; break;
-      case JvOp::Sub: r = a.scalarVal - b.scalarVal; break;
-      case JvOp::Mul: r = a.scalarVal * b.scalarVal; break;
-      case JvOp::Div: r = a.scalarVal / b.scalarVal; break;
-    }
-    return jvScalar<T>(r, a.N);
+    return dispatchOp(op, [&](auto opTag) {
+      return jvScalar<T>(
+          binaryValue<decltype(opTag)::value>(a.scalarVal, b.scalarVal), a.N);
+    });
   }
   JetVec<T> out = denseLike(a, b);
-  switch (op) {
-    case JvOp::Add: dispatchBinary<T, 0>(a, b, out); break;
-    case JvOp::Sub: dispatchBinary<T, 1>(a, b, out); break;
-    case JvOp::Mul: dispatchBinary<T, 2>(a, b, out); break;
-    case JvOp::Div: dispatchBinary<T, 3>(a, b, out); break;
-  }
+  dispatchOp(op, [&](auto opTag) {
+    dispatchKind(a.kind(), [&](auto ka) {
+      dispatchKind(b.kind(), [&](auto kb) {
+        constexpr JvKind KA = decltype(ka)::value, KB = decltype(kb)::value;
+        if constexpr (KA == JvKind::SCALAR && KB == JvKind::SCALAR) {
+          MEGBA_CHECK(false, "scalar op scalar is not a JetVector op");
+        } else {
+          forEachItem(out.onGpu, out.nItem,
+                      BinaryItem<T, decltype(opTag)::value, KA, KB>{
+                          makeOperand<T, KA>(a), makeOperand<T, KB>(b),
+                          out.nItem, out.N, out.value->ptr, out.grad->ptr});
+        }
+      });
+    });
+  });
   return out;
 }
 
 template <typename T>
 JetVec<T> jvUnary(JvUnary op, const JetVec<T>& a) {
   MEGBA_CHECK(!a.isScalar, "unary op needs a vector operand");
-  JetVec<T> out = denseLike(a, a);
-  const int agKind = (int)a.kind();
-  const T* ag = a.grad ? a.grad->ptr : nullptr;
-  const int OP = (int)op;
-  if (out.onGpu) {
-    switch (OP) {
-      case 0: hipLaunchKernelGGL((kJvUnary<T, 0>), dim3(jvGrid(a.nItem)), dim3(256), 0, 0, a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-      case 1: hipLaunchKernelGGL((kJvUnary<T, 1>), dim3(jvGrid(a.nItem)), dim3(256), 0, 0, a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-      case 2: hipLaunchKernelGGL((kJvUnary<T, 2>), dim3(jvGrid(a.nItem)), dim3(256), 0, 0, a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-      case 3: hipLaunchKernelGGL((kJvUnary<T, 3>), dim3(jvGrid(a.nItem)), dim3(256), 0, 0, a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-      case 4: hipLaunchKernelGGL((kJvUnary<T, 4>), dim3(jvGrid(a.nItem)), dim3(256), 0, 0, a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-    }
-    JV_HIP_CHECK(hipGetLastError());
-  } else {
-    switch (OP) {
-      case 0: cpuJvUnary<T, 0>(a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-      case 1: cpuJvUnary<T, 1>(a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-      case 2: cpuJvUnary<T, 2>(a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-      case 3: cpuJvUnary<T, 3>(a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-      case 4: cpuJvUnary<T, 4>(a.value->ptr, a.nItem, a.N, ag, a.gradPos, agKind, out.value->ptr, out.grad->ptr); break;
-    }
-  }
+  JetVec<T> out = denseLike(a);
+  dispatchUnary(op, [&](auto opTag) {
+    dispatchVectorKind(a, [&](auto k) {
+      constexpr JvKind K = decltype(k)::value;
+      forEachItem(out.onGpu, out.nItem,
+                  UnaryItem<T, decltype(opTag)::value, K>{
+                      makeOperand<T, K>(a), out.nItem, out.N, out.value->ptr,
+                      out.grad->ptr});
+    });
+  });
   return out;
 }
 
@@ -436,37 +508,19 @@ std::vector<JetVec<T>> jvAngleAxisToRotation(const std::vector<JetVec<T>>& aa) {
   return R;
 }
 
+// The wrap has a per-item branch (floor), so it is a body of its own and not
+// a composition of elementwise ops.
 template <typename T>
 JetVec<T> jvNormalizeAngle(const JetVec<T>& theta) {
   MEGBA_CHECK(!theta.isScalar, "normalize_angle needs a vector operand");
-  // wrap = theta - 2*pi*round(theta / (2*pi)); d wrap / d theta = 1
-  const int64_t n = theta.nItem;
-  JetVec<T> out;
-  out.nItem = n;
-  out.N = theta.N;
-  out.onGpu = theta.onGpu;
-  out.value = makeBuf<T>(n, out.onGpu);
-  out.grad = makeBuf<T>((int64_t)out.N * n, out.onGpu);
-  // value: via composition would lose the per-item branch; do it directly.
-  std::vector<T> hv(n), hg((int64_t)out.N * n);
-  jvToHost(theta, hv.data(), hg.data());
-  const T twoPi = T(6.283185307179586476925286766559);
-  for (int64_t i = 0; i < n; ++i) {
-    T v = hv[i];
-    v = v - twoPi * (T)std::floor(((double)v + 3.14159265358979323846) /
-                                  (double)twoPi);
-    hv[i] = v;
-  }
-  if (out.onGpu) {
-    JV_HIP_CHECK(hipMemcpy(out.value->ptr, hv.data(), n * sizeof(T),
-                           hipMemcpyHostToDevice));
-    JV_HIP_CHECK(hipMemcpy(out.grad->ptr, hg.data(),
-                           (int64_t)out.N * n * sizeof(T),
-                           hipMemcpyHostToDevice));
-  } else {
-    std::memcpy(out.value->ptr, hv.data(), n * sizeof(T));
-    std::memcpy(out.grad->ptr, hg.data(), (int64_t)out.N * n * sizeof(T));
-  }
+  JetVec<T> out = denseLike(theta);
+  dispatchVectorKind(theta, [&](auto k) {
+    constexpr JvKind K = decltype(k)::value;
+    forEachItem(out.onGpu, out.nItem,
+                NormalizeAngleItem<T, K>{makeOperand<T, K>(theta), out.nItem,
+                                         out.N, out.value->ptr,
+                                         out.grad->ptr});
+  });
   return out;
 }
 template JetVec<double> jvNormalizeAngle<double>(const JetVec<double>&);
@@ -520,154 +574,26 @@ JetVec<T> jvRadialDistortion(const std::vector<JetVec<T>>& p,
   return intr[0] * d;
 }
 
-// Rotation matrix -> unit quaternion [w,x,y,z] with gradients: per-item
-// Shepperd branch on the largest of {trace, R00, R11, R22} (the reference's
-// RotationToQuaternion kernel, quaternion.cu:102-199, used a static device
-// function-pointer table; here one parameterised branch).  Inputs must be
-// dense JetVectors (geometry-op outputs are).
-namespace {
-template <typename T>
-__global__ void kRot2Quat(int64_t n, int N, const T* const* rv,
-                          const T* const* rg, T* const* qv, T* const* qg) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    T v[9], q[4];
-    for (int k = 0; k < 9; ++k) v[k] = rv[k][i];
-    // local dense copies of grads are too large for registers at runtime N:
-    // recompute via the strided helper form instead.
-    // Build strided accessors: helper expects gr[(k*N+g)*n]; we emulate by
-    // copying pointers — instead call a small inline with direct indexing:
-    const T tr = v[0] + v[4] + v[8];
-    int b = 0;
-    T best = tr;
-    if (v[0] > best) { b = 1; best = v[0]; }
-    if (v[4] > best) { b = 2; best = v[4]; }
-    if (v[8] > best) { b = 3; }
-    const T sg[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
-    const int major[4] = {0, 1, 2, 3};
-    const int oth[4][3][4] = {
-        {{1, 7, 5, -1}, {2, 2, 6, -1}, {3, 3, 1, -1}},
-        {{0, 7, 5, -1}, {2, 3, 1, +1}, {3, 2, 6, +1}},
-        {{0, 2, 6, -1}, {1, 3, 1, +1}, {3, 7, 5, +1}},
-        {{0, 3, 1, -1}, {1, 2, 6, +1}, {2, 7, 5, +1}}};
-    const T t = T(1) + sg[b][0] * v[0] + sg[b][1] * v[4] + sg[b][2] * v[8];
-    const T s = ::sqrt(t);
-    const T inv2s = T(0.5) / s;
-    q[major[b]] = s * T(0.5);
-    T comp[3];
-    for (int k = 0; k < 3; ++k) {
-      comp[k] = (v[oth[b][k][1]] + T(oth[b][k][3]) * v[oth[b][k][2]]) * inv2s;
-      q[oth[b][k][0]] = comp[k];
-    }
-    for (int k = 0; k < 4; ++k) qv[k][i] = q[k];
-    for (int g = 0; g < N; ++g) {
-      const T dt = sg[b][0] * rg[0][(int64_t)g * n + i] +
-                   sg[b][1] * rg[4][(int64_t)g * n + i] +
-                   sg[b][2] * rg[8][(int64_t)g * n + i];
-      const T ds = dt * inv2s;
-      qg[major[b]][(int64_t)g * n + i] = ds * T(0.5);
-      for (int k = 0; k < 3; ++k) {
-        const T dn = rg[oth[b][k][1]][(int64_t)g * n + i] +
-                     T(oth[b][k][3]) * rg[oth[b][k][2]][(int64_t)g * n + i];
-        qg[oth[b][k][0]][(int64_t)g * n + i] = dn * inv2s - comp[k] * ds / s;
-      }
-    }
-  }
-}
-}  // namespace
-
+// Inputs must be dense JetVectors (geometry-op outputs are).
 template <typename T>
 std::vector<JetVec<T>> jvRotationToQuaternion(const std::vector<JetVec<T>>& R) {
   MEGBA_CHECK(R.size() == 9, "rotation needs 9 components");
   for (const auto& r : R)
     MEGBA_CHECK(r.kind() == JvKind::DENSE, "rot->quat needs dense JetVectors");
-  const int64_t n = R[0].nItem;
-  const int N = R[0].N;
-  const bool gpu = R[0].onGpu;
   std::vector<JetVec<T>> q;
-  for (int k = 0; k < 4; ++k) {
-    JetVec<T> o;
-    o.nItem = n;
-    o.N = N;
-    o.onGpu = gpu;
-    o.value = makeBuf<T>(n, gpu);
-    o.grad = makeBuf<T>((int64_t)N * n, gpu);
-    q.push_back(o);
-  }
-  std::vector<const T*> rv(9), rg(9);
-  std::vector<T*> qvp(4), qgp(4);
+  Rot2QuatItem<T> body;
+  body.n = R[0].nItem;
+  body.N = R[0].N;
   for (int k = 0; k < 9; ++k) {
-    rv[k] = R[k].value->ptr;
-    rg[k] = R[k].grad->ptr;
+    body.rv[k] = R[k].value->ptr;
+    body.rg[k] = R[k].grad->ptr;
   }
   for (int k = 0; k < 4; ++k) {
-    qvp[k] = q[k].value->ptr;
-    qgp[k] = q[k].grad->ptr;
+    q.push_back(denseLike(R[0]));
+    body.qv[k] = q[k].value->ptr;
+    body.qg[k] = q[k].grad->ptr;
   }
-  if (gpu) {
-    // pointer tables on device
-    const T** drv;
-    const T** drg;
-    T** dqv;
-    T** dqg;
-    JV_HIP_CHECK(hipMalloc(&drv, 9 * sizeof(T*)));
-    JV_HIP_CHECK(hipMalloc(&drg, 9 * sizeof(T*)));
-    JV_HIP_CHECK(hipMalloc(&dqv, 4 * sizeof(T*)));
-    JV_HIP_CHECK(hipMalloc(&dqg, 4 * sizeof(T*)));
-    JV_HIP_CHECK(hipMemcpy(drv, rv.data(), 9 * sizeof(T*), hipMemcpyHostToDevice));
-    JV_HIP_CHECK(hipMemcpy(drg, rg.data(), 9 * sizeof(T*), hipMemcpyHostToDevice));
-    JV_HIP_CHECK(hipMemcpy(dqv, qvp.data(), 4 * sizeof(T*), hipMemcpyHostToDevice));
-    JV_HIP_CHECK(hipMemcpy(dqg, qgp.data(), 4 * sizeof(T*), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kRot2Quat<T>, dim3(jvGrid(n)), dim3(256), 0, 0, n, N,
-                       drv, drg, dqv, dqg);
-    JV_HIP_CHECK(hipGetLastError());
-    JV_HIP_CHECK(hipDeviceSynchronize());
-    (void)hipFree(drv);
-    (void)hipFree(drg);
-    (void)hipFree(dqv);
-    (void)hipFree(dqg);
-  } else {
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < n; ++i) {
-      T v[9], qq[4];
-      for (int k = 0; k < 9; ++k) v[k] = rv[k][i];
-      const T tr = v[0] + v[4] + v[8];
-      int b = 0;
-      T best = tr;
-      if (v[0] > best) { b = 1; best = v[0]; }
-      if (v[4] > best) { b = 2; best = v[4]; }
-      if (v[8] > best) { b = 3; }
-      const T sg[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
-      const int major[4] = {0, 1, 2, 3};
-      const int oth[4][3][4] = {
-          {{1, 7, 5, -1}, {2, 2, 6, -1}, {3, 3, 1, -1}},
-          {{0, 7, 5, -1}, {2, 3, 1, +1}, {3, 2, 6, +1}},
-          {{0, 2, 6, -1}, {1, 3, 1, +1}, {3, 7, 5, +1}},
-          {{0, 3, 1, -1}, {1, 2, 6, +1}, {2, 7, 5, +1}}};
-      const T t = T(1) + sg[b][0] * v[0] + sg[b][1] * v[4] + sg[b][2] * v[8];
-      const T s = std::sqrt(t);
-      const T inv2s = T(0.5) / s;
-      qq[major[b]] = s * T(0.5);
-      T comp[3];
-      for (int k = 0; k < 3; ++k) {
-        comp[k] = (v[oth[b][k][1]] + T(oth[b][k][3]) * v[oth[b][k][2]]) * inv2s;
-        qq[oth[b][k][0]] = comp[k];
-      }
-      for (int k = 0; k < 4; ++k) qvp[k][i] = qq[k];
-      for (int g = 0; g < N; ++g) {
-        const T dt = sg[b][0] * rg[0][(int64_t)g * n + i] +
-                     sg[b][1] * rg[4][(int64_t)g * n + i] +
-                     sg[b][2] * rg[8][(int64_t)g * n + i];
-        const T ds = dt * inv2s;
-        qgp[major[b]][(int64_t)g * n + i] = ds * T(0.5);
-        for (int k = 0; k < 3; ++k) {
-          const T dn = rg[oth[b][k][1]][(int64_t)g * n + i] +
-                       T(oth[b][k][3]) * rg[oth[b][k][2]][(int64_t)g * n + i];
-          qgp[oth[b][k][0]][(int64_t)g * n + i] = dn * inv2s - comp[k] * ds / s;
-        }
-      }
-    }
-  }
+  forEachItem(R[0].onGpu, body.n, body);
   return q;
 }
 template std::vector<JetVec<double>> jvRotationToQuaternion<double>(

@@ -5,14 +5,16 @@
 // src/operator/jet_vector_math_impl.cu): every scalar in a residual
 // expression is a vector over nItem observations with an N-wide dual part.
 // Three operand kinds (the reference's 39 hand-written kernel variants are
-// generated here from one template over {DENSE, JPV, SCALAR}):
+// generated here from one per-item body per op, a template over the op and
+// {DENSE, JPV, SCALAR}, shared by the HIP and the CPU backend):
 //   DENSE  — value[nItem] + grad[N][nItem] (grad-major, like the reference's
 //            grad layout ptr[tid + i*nItem])
 //   JPV    — leaf parameter: value only, gradient is the implicit unit
 //            vector e_{gradPos} (reference's _gradPosition optimisation)
 //   SCALAR — broadcast host scalar (reference's _pureScalarFlag)
-// Ops run on GPU (HIP kernels, one thread per item, runtime-N lane loop) or
-// CPU (OpenMP).  This layer powers runtime user-defined edges; the built-in
+// Ops run on GPU (one grid-stride HIP kernel per body, one item per thread
+// and trip, runtime-N gradient loop) or CPU (OpenMP over the same body).
+// This layer powers runtime user-defined edges; the built-in
 // BAL edge uses the fused register-autodiff kernel instead (gpu_engine.hip),
 // which is the performance path.
 #pragma once
@@ -83,7 +85,7 @@ JetVec<T> jvUnary(JvUnary op, const JetVec<T>& a);
 // aa[3] -> row-major R[9]
 template <typename T>
 std::vector<JetVec<T>> jvAngleAxisToRotation(const std::vector<JetVec<T>>& aa);
-// wrap theta to (-pi, pi], gradient unchanged (reference SE2
+// wrap theta to [-pi, pi), gradient unchanged (reference SE2
 // normalize_rotation2D_Kernel)
 template <typename T>
 JetVec<T> jvNormalizeAngle(const JetVec<T>& theta);

@@ -290,3 +290,139 @@ def test_normalize_angle_cpu():
     np.testing.assert_allclose(v, ref, atol=1e-12)
     assert (v > -np.pi - 1e-12).all() and (v <= np.pi + 1e-12).all()
     np.testing.assert_allclose(g[0], np.ones(50))
+    # DENSE input with a random gradient, boundary values, JPV on the same
+    # values: the gradient passes through unchanged.
+    th, gin, (v, g), (vj, gj) = normalize_angle_cases(False)
+    ref = th - 2 * np.pi * np.floor((th + np.pi) / (2 * np.pi))
+    np.testing.assert_allclose(v, ref, atol=1e-12)
+    assert (v >= -np.pi - 1e-12).all() and (v < np.pi + 1e-12).all()
+    assert np.array_equal(g, gin)
+    assert np.array_equal(vj, v)
+    assert np.array_equal(gj, Ref.leaf(th, 1).g)
+
+
+ANGLE_EDGES = np.array([-np.pi, np.pi, 3 * np.pi, 0.0])
+
+
+def normalize_angle_cases(gpu):
+    """normalize_angle of a DENSE and a JPV operand over random angles plus
+    the wrap boundaries, exact and 1e-12 to either side."""
+    r = np.random.default_rng(5)
+    th = np.concatenate([r.normal(scale=6.0, size=50), ANGLE_EDGES,
+                         ANGLE_EDGES - 1e-12, ANGLE_EDGES + 1e-12])
+    gin = r.normal(size=(N, len(th)))
+    d = _core.jv_normalize_angle(_core.JetVector(th, gin, N=N, gpu=gpu))
+    j = _core.jv_normalize_angle(
+        _core.JetVector(th, None, N=N, grad_pos=1, gpu=gpu))
+    return th, gin, d.to_numpy(), j.to_numpy()
+
+
+@pytest.mark.gpu
+def test_normalize_angle_gpu_equals_cpu():
+    # Same IEEE operations on both backends: bit for bit.
+    _, _, (v, g), (vj, gj) = normalize_angle_cases(False)
+    _, _, (v2, g2), (vj2, gj2) = normalize_angle_cases(True)
+    assert np.array_equal(v2, v) and np.array_equal(g2, g)
+    assert np.array_equal(vj2, vj) and np.array_equal(gj2, gj)
+
+
+UNARY = [(_core.jv_neg, lambda v: -v, lambda v: -np.ones_like(v)),
+         (_core.jv_abs, np.abs, np.sign),
+         (_core.jv_sin, np.sin, np.cos),
+         (_core.jv_cos, np.cos, lambda v: -np.sin(v)),
+         (_core.jv_sqrt, np.sqrt, lambda v: 0.5 / np.sqrt(v))]
+
+
+def run_unary_kinds(gpu):
+    """All five unary ops on a DENSE and on a JPV operand."""
+    r = np.random.default_rng(11)
+    for op, f, df in UNARY:
+        v = r.normal(size=NI) + 3.0
+        if op is _core.jv_abs:
+            v[::2] -= 6.0  # half the items negative
+            assert (v < 0).sum() > NI // 4 and (v > 0).sum() > NI // 4
+        if op is _core.jv_sqrt:
+            v = np.abs(v) + 0.5
+        g = r.normal(size=(N, NI))
+        for jv_in, rin in (
+                (_core.JetVector(v, g, N=N, gpu=gpu), Ref(v, g)),
+                (_core.JetVector(v, None, N=N, grad_pos=2, gpu=gpu),
+                 Ref.leaf(v, 2))):
+            ov, og = op(jv_in).to_numpy()
+            np.testing.assert_allclose(ov, f(v))
+            np.testing.assert_allclose(og, df(v) * rin.g)
+
+
+def test_unary_kinds_cpu():
+    run_unary_kinds(False)
+
+
+@pytest.mark.gpu
+def test_unary_kinds_gpu():
+    run_unary_kinds(True)
+
+
+def rot2quat_case(gpu):
+    """The q -> R -> q' chain of the round-trip test on fixed inputs; returns
+    q and the (value, grad) pairs of q'."""
+    ni = 64
+    r = np.random.default_rng(3)
+    q_val = r.normal(size=(4, ni))
+    q_val /= np.linalg.norm(q_val, axis=0, keepdims=True)
+    q_val[:, ::4] = np.abs(q_val[:, ::4])
+    q = [_core.JetVector(q_val[i], None, N=4, grad_pos=i, gpu=gpu)
+         for i in range(4)]
+    q2 = _core.jv_rotation_to_quaternion(_core.jv_quaternion_to_rotation(q))
+    return q_val, [q2[k].to_numpy() for k in range(4)]
+
+
+def shepperd_branch(q_val):
+    w, x, y, z = q_val
+    r00 = 1 - 2 * (y * y + z * z)
+    r11 = 1 - 2 * (x * x + z * z)
+    r22 = 1 - 2 * (x * x + y * y)
+    return np.argmax(np.stack([r00 + r11 + r22, r00, r11, r22]), axis=0)
+
+
+@pytest.mark.gpu
+def test_rotation_to_quaternion_gpu_equals_cpu():
+    """GPU q -> R -> q' equals the CPU backend's to rtol=1e-12.
+
+    The bound has no absolute floor, and the gradients of the minor
+    components hold differences that cancel, to exactly 0 where q' does not
+    depend on the parameter.  The rounding residue left there (order 1e-16)
+    depends on whether a*b + c*d is fused; the Shepperd body is therefore
+    compiled without FMA contraction, and every product feeding it here has
+    a 0/1 or scalar factor, so the two backends agree bit for bit.  With a
+    contracting device build 51, 31, 33 and 38 of the 256 gradient entries
+    of q'[0..3] miss the bound (largest absolute difference 2.2e-16).
+    """
+    q_val, ref = rot2quat_case(False)
+    _, out = rot2quat_case(True)
+    # every Shepperd branch is taken by some items
+    assert (np.bincount(shepperd_branch(q_val), minlength=4) >= 4).all()
+    for k in range(4):
+        for part in (0, 1):
+            d = np.abs(out[k][part] - ref[k][part])
+            bad = d > 1e-12 * np.abs(ref[k][part])
+            print(f"q'[{k}] {'value' if part == 0 else 'grad'}: "
+                  f"max abs diff {d.max():.3g}, {bad.sum()} of {d.size} "
+                  f"beyond rtol, largest |ref| among them "
+                  f"{np.abs(ref[k][part][bad]).max() if bad.any() else 0:.3g}")
+    for k in range(4):
+        np.testing.assert_allclose(out[k][0], ref[k][0], rtol=1e-12)
+        np.testing.assert_allclose(out[k][1], ref[k][1], rtol=1e-12)
+
+
+@pytest.mark.gpu
+def test_binary_grid_stride_gpu():
+    # One item more than 4096 blocks x 256 threads cover in one trip, plus an
+    # odd tail: some threads take a second trip through the grid-stride loop.
+    ni = 4096 * 256 + 257
+    r = np.random.default_rng(7)
+    av, ag, bv = r.normal(size=ni), r.normal(size=(1, ni)), r.normal(size=ni)
+    a = _core.JetVector(av, ag, N=1, gpu=True)
+    b = _core.JetVector(bv, None, N=1, grad_pos=0, gpu=True)
+    v, g = _core.jv_mul(a, b).to_numpy()
+    np.testing.assert_allclose(v, av * bv, rtol=1e-12, atol=1e-13)
+    np.testing.assert_allclose(g, ag * bv + av, rtol=1e-12, atol=1e-13)
