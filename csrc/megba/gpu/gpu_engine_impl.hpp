@@ -65,10 +65,11 @@ namespace megba {
 
 // Which kernels form the local E Cinv E^T x product of a PCG iteration.
 enum class SchurPath {
-  Lds,       // kSchurFusedLds + row reduce (single pass, LDS accumulator)
-  FusedEtx,  // kEtxCinvFused, then E w (default)
-  Separate,  // E^T x, Cinv, E w as separate passes
-  OnePass,   // kSchurFused (MEGBA_FUSED)
+  Lds,           // kSchurFusedLds + row reduce (single pass, LDS accumulator)
+  LdsRecompute,  // kSchurFusedLdsRc: Lds with the BAL J rebuilt per edge
+  FusedEtx,      // kEtxCinvFused, then E w (default)
+  Separate,      // E^T x, Cinv, E w as separate passes
+  OnePass,       // kSchurFused (MEGBA_FUSED)
 };
 
 // What one PCG iteration launches.  Resolved once at the first solve
@@ -93,6 +94,7 @@ class GpuEngine final : public Engine<T> {
   static constexpr int CR = CD * RD;            // Jc values per edge
   static constexpr int PR = PD * RD;            // Jp values per edge
   static constexpr int RW = RD * (RD + 1) / 2;  // packed info entries
+  static constexpr bool kBalDims = CD == 9 && PD == 3 && RD == 2;
   using PkJ = PackedEdge<T, CD, PD, RD, true>;   // implicit [Jc, Jp] groups
   using PkH = PackedEdge<T, CD, PD, RD, false>;  // explicit Hpl groups
 
@@ -344,6 +346,19 @@ class GpuEngine final : public Engine<T> {
     cur_ ^= 1;          // accepted set = dX_[cur_^1]
     freshCur_ = false;  // the (new) current buffers are not yet written
     updateJSlots();
+    // the recompute path rebuilds J from the point it was evaluated at, which
+    // dParams_ holds now and stops holding at the next updateParams()
+    if (rcEligible_ && (!plan_ || plan_->path == SchurPath::LdsRecompute))
+      snapshotAccepted();
+  }
+
+  // Camera rows and 4-padded local points of the accepted linearisation
+  // point (kBalSnapshot), read by kSchurFusedLdsRc alone.
+  void snapshotAccepted() {
+    if constexpr (kBalDims)
+      hipLaunchKernelGGL(kBalSnapshot<T>, dim3(gridFor((int64_t)ncam_ + npL_)),
+                         dim3(kBlk), 0, stream_, ncam_, ptLo_, npL_, dParams_,
+                         dCamAux_, dPtAcc_);
   }
 
   // Point the device slots at the accepted (bak) buffer set.
@@ -844,9 +859,10 @@ class GpuEngine final : public Engine<T> {
     // back), also when MEGBA_FUSED then overrides the product
     if (knobs_.tuneVerbose)
       fprintf(stderr, "# schur path: %s\n",
-              tuned == SchurPath::Lds        ? "lds"
-              : tuned == SchurPath::FusedEtx ? "fused-etx"
-                                             : "separate");
+              tuned == SchurPath::Lds            ? "lds"
+              : tuned == SchurPath::LdsRecompute ? "lds-recompute"
+              : tuned == SchurPath::FusedEtx     ? "fused-etx"
+                                                 : "separate");
     PcgPlan plan;
     plan.path = knobs_.fused ? SchurPath::OnePass : tuned;
     plan.rotatedBody = !knobs_.noPcgFuse;
@@ -855,8 +871,9 @@ class GpuEngine final : public Engine<T> {
     // row reduce, B-apply and dot in one kernel when nothing sits between
     // them: LDS path, no long-run finishers, no collective
     plan.mergeReduceBApply = plan.rotatedBody &&
-                             plan.path == SchurPath::Lds && nLongPts_ == 0 &&
-                             allreduceIsNoop();
+                             (plan.path == SchurPath::Lds ||
+                              plan.path == SchurPath::LdsRecompute) &&
+                             nLongPts_ == 0 && allreduceIsNoop();
     return plan;
   }
   // One-time measured choice between the fused E^T x + Cinv window kernel
@@ -874,15 +891,31 @@ class GpuEngine final : public Engine<T> {
   // the tuning threshold reach it), MEGBA_NO_SCHUR_LDS removes it; forcing
   // one of the two-pass variants (MEGBA_NO_ETXFUSE / MEGBA_ETXFUSE) leaves
   // it out as well.
+  //
+  // The recomputed-J form of the LDS apply (SchurPath::LdsRecompute) is a
+  // fourth candidate under its own eligibility (setupSchurLds) and the same
+  // rules: MEGBA_SCHUR_RECOMPUTE forces it when eligible and then wins over
+  // MEGBA_SCHUR_LDS, MEGBA_NO_SCHUR_RECOMPUTE removes it, and where it is
+  // not eligible its forcing knob changes nothing.
   SchurPath chooseSchurPath() {
     const SchurPath twoPass =
         knobs_.noEtxFuse ? SchurPath::Separate : SchurPath::FusedEtx;
     const bool twoPassForced = knobs_.noEtxFuse || knobs_.etxFuse;
     const bool ldsForced = knobs_.schurLds;
+    const bool rcForced = knobs_.schurRecompute;
+    const bool tuning = !twoPassForced && nL_ >= 200000;
     bool lds = ldsEligible_ && (!twoPassForced || ldsForced);
+    bool rc = rcEligible_ && (rcForced || (tuning && !ldsForced));
+    if (rc) {
+      // first launch outside any graph capture, as for the LDS apply below
+      (void)hipGetLastError();
+      schurFusedLdsEcE({dDeltaX_, false}, dQ_, false, /*recompute=*/true);
+      if (hipGetLastError() != hipSuccess) rc = false;
+    }
+    if (rcForced && rc) return SchurPath::LdsRecompute;
     // nothing to choose: a forced two-pass variant, or the launch-noise
     // regime, where the default stays
-    if (!ldsForced && (twoPassForced || nL_ < 200000)) return twoPass;
+    if (!ldsForced && !tuning) return twoPass;
     if (lds) {
       // first launch happens here, outside any graph capture: a launch the
       // runtime refuses (LDS size) drops the candidate instead of failing
@@ -894,11 +927,12 @@ class GpuEngine final : public Engine<T> {
     hipEvent_t ev[2];
     HIP_CHECK(hipEventCreate(&ev[0]));
     HIP_CHECK(hipEventCreate(&ev[1]));
-    float ms[3] = {0, 0, 0};
-    const SchurPath variants[3] = {SchurPath::FusedEtx, SchurPath::Separate,
-                                   SchurPath::Lds};
-    const int nVar = lds ? 3 : 2;
-    for (int variant = 0; variant < nVar; ++variant) {
+    float ms[4] = {0, 0, 0, 0};
+    const SchurPath variants[4] = {SchurPath::FusedEtx, SchurPath::Separate,
+                                   SchurPath::Lds, SchurPath::LdsRecompute};
+    const bool timed[4] = {true, true, lds, rc};
+    for (int variant = 0; variant < 4; ++variant) {
+      if (!timed[variant]) continue;
       // warm-up then timed triple (dQ_/dWPad_/dTemp_ are scratch)
       localSchurEcE(variants[variant], {dDeltaX_, false}, dQ_);
       HIP_CHECK(hipEventRecord(ev[0], stream_));
@@ -915,8 +949,13 @@ class GpuEngine final : public Engine<T> {
               "# schur autotune: fused-etx %.3f ms, separate %.3f ms, "
               "lds %.3f ms (3 applies each)\n",
               ms[0], ms[1], lds ? ms[2] : -1.0f);
+    if (knobs_.tuneVerbose && rc)
+      fprintf(stderr, "# schur recompute: %.3f ms (3 applies)\n", ms[3]);
     (void)hipEventDestroy(ev[0]);
     (void)hipEventDestroy(ev[1]);
+    // the recompute candidate only when it is the fastest of all
+    if (rc && ms[3] < ms[best2] && (!lds || ms[3] < ms[2]))
+      return SchurPath::LdsRecompute;
     return useLds ? SchurPath::Lds : variants[best2];
   }
 
@@ -937,6 +976,24 @@ class GpuEngine final : public Engine<T> {
       return (const void*)kSchurFusedLds<T, CD, PD, RD, decltype(im)::value,
                                          decltype(hi)::value>;
     });
+  }
+  // The same for kSchurFusedLdsRc, which exists for the BAL dims only.
+  const void* schurLdsRcKernel() const {
+    if constexpr (kBalDims)
+      return hasInfo_ ? (const void*)kSchurFusedLdsRc<T, true>
+                      : (const void*)kSchurFusedLdsRc<T, false>;
+    return nullptr;
+  }
+  void launchSchurLdsRc(size_t ldsBytes) {
+    if constexpr (kBalDims)
+      dispatchBool(hasInfo_, [&](auto infoTag) {
+        hipLaunchKernelGGL(
+            (kSchurFusedLdsRc<T, decltype(infoTag)::value>), dim3(numCU_),
+            dim3(rcThreads_), ldsBytes, stream_, nWin_, dWinLo_, dWinHi_,
+            dWinFlag_, nL_, dCamOf_, dPtOf_, dCamAux_, dPtAcc_, dCamFixed_,
+            dPtFixed_, (const T* const*)dJSlots_, dInfo_, lossKind_, lossD2_,
+            dXPad_, dHllInv_, dTemp_, (int)nc_, dLdsRows_);
+      });
   }
   // Grid of the one-wave-per-window kernels (4 waves per block).
   static int windowGrid(int nWin) {
@@ -1025,25 +1082,56 @@ class GpuEngine final : public Engine<T> {
     }
     dLdsRows_ = dalloc<T>((int64_t)numCU_ * nc_);
     ldsEligible_ = true;
+    // Recomputed-J form: built-in BAL residual, implicit mode.  Its buffers
+    // are allocated here, once, so the captured PCG graph sees stable
+    // pointers; acceptForward fills them.
+    if constexpr (kBalDims) {
+      if (!implicit_ || customFwd_ || knobs_.noSchurRecompute) return;
+      if (hipFuncSetAttribute(schurLdsRcKernel(),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)need) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+      }
+      // its own workgroup size: 512 measured faster than 1024 and is the
+      // kernel's launch bound; the development knob applies up to that
+      rcThreads_ = ldsThreads_ < kLdsRcMaxThreads && knobs_.schurLdsThreads
+                       ? ldsThreads_
+                       : kLdsRcMaxThreads;
+      dCamAux_ = dalloc<T>((int64_t)ncam_ * kBalCamRow);
+      dPtAcc_ = dalloc<T>((int64_t)npt_ * 4);
+      HIP_CHECK(hipMemsetAsync(dCamAux_, 0,
+                               (int64_t)ncam_ * kBalCamRow * sizeof(T),
+                               stream_));
+      HIP_CHECK(hipMemsetAsync(dPtAcc_, 0, (int64_t)npt_ * 4 * sizeof(T),
+                               stream_));
+      rcEligible_ = true;
+    }
   }
 
   // out = E Cinv E^T x (local part) in one pass over the primary-sorted J
   // with a per-workgroup LDS accumulator; out is fully overwritten.  With
   // bApplyDot the row reduce carries on to out = HppD x - out and the x.out
   // partials (dPartQ_), which needs nLongPts_ == 0.
-  void schurFusedLdsEcE(XIn x, T* out, bool bApplyDot = false) {
+  // With recompute the window kernel is kSchurFusedLdsRc, which rebuilds the
+  // implicit edge from the accepted snapshot instead of reading dJPk_.
+  void schurFusedLdsEcE(XIn x, T* out, bool bApplyDot = false,
+                        bool recompute = false) {
     windowPrologue(x);
     const size_t ldsBytes = (size_t)nc_ * sizeof(T);
-    dispatchMode([&](auto impTag, auto infoTag) {
-      constexpr bool IM = decltype(impTag)::value;
-      constexpr bool HI = decltype(infoTag)::value;
-      hipLaunchKernelGGL((kSchurFusedLds<T, CD, PD, RD, IM, HI>),
-                         dim3(numCU_), dim3(ldsThreads_), ldsBytes, stream_,
-                         nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
-                         dPtOf_, dHpl_, dJPk_, (const T* const*)dJSlots_,
-                         dInfo_, lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_,
-                         (int)nc_, dLdsRows_);
-    });
+    if (recompute)
+      launchSchurLdsRc(ldsBytes);
+    else
+      dispatchMode([&](auto impTag, auto infoTag) {
+        constexpr bool IM = decltype(impTag)::value;
+        constexpr bool HI = decltype(infoTag)::value;
+        hipLaunchKernelGGL((kSchurFusedLds<T, CD, PD, RD, IM, HI>),
+                           dim3(numCU_), dim3(ldsThreads_), ldsBytes, stream_,
+                           nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
+                           dPtOf_, dHpl_, dJPk_, (const T* const*)dJSlots_,
+                           dInfo_, lossKind_, lossD2_, dXPad_, dHllInv_,
+                           dTemp_, (int)nc_, dLdsRows_);
+      });
     if (bApplyDot) {
       hipLaunchKernelGGL((kLdsReduceBApplyDot<T, CD>), dim3(ldsReduceGrid()),
                          dim3(64 * kLdsRedWaves), 0, stream_, numCU_, (int)nc_,
@@ -1057,11 +1145,14 @@ class GpuEngine final : public Engine<T> {
   }
 
   // local (collective-free) E Cinv E^T x into out on the given path: one of
-  // the tuner's three candidates (schurApply launches OnePass itself)
+  // the tuner's four candidates (schurApply launches OnePass itself)
   void localSchurEcE(SchurPath path, XIn x, T* out) {
     switch (path) {
       case SchurPath::Lds:
         schurFusedLdsEcE(x, out);
+        break;
+      case SchurPath::LdsRecompute:
+        schurFusedLdsEcE(x, out, false, /*recompute=*/true);
         break;
       case SchurPath::FusedEtx:
         etxCinv(x);
@@ -1263,7 +1354,8 @@ class GpuEngine final : public Engine<T> {
   // returns how many partials it wrote to dPartQ_ (0 without withDot).
   int schurApply(XIn x, T* q, bool withDot) {
     if (withDot && plan_->mergeReduceBApply) {
-      schurFusedLdsEcE(x, q, /*bApplyDot=*/true);
+      schurFusedLdsEcE(x, q, /*bApplyDot=*/true,
+                       plan_->path == SchurPath::LdsRecompute);
       return ldsReduceGrid();
     }
     if (plan_->path == SchurPath::OnePass)
@@ -1306,6 +1398,12 @@ class GpuEngine final : public Engine<T> {
   int numCU_ = 0;
   int ldsThreads_ = 1024;
   T* dLdsRows_{};  // [numCU_][nc_] per-workgroup flush rows
+  // Recomputed-J LDS apply (kSchurFusedLdsRc): eligibility and the snapshot
+  // of the accepted linearisation point that acceptForward refreshes.
+  bool rcEligible_ = false;
+  int rcThreads_ = kLdsRcMaxThreads;
+  T* dCamAux_{};  // [ncam_][kBalCamRow] balCameraPart rows
+  T* dPtAcc_{};   // [npt_][4] accepted points, 4-padded, global point id
   int nWin_ = 0, nFlagWins_ = 0, nLongPts_ = 0;
   int64_t* dWinLo_{};
   int64_t* dWinHi_{};

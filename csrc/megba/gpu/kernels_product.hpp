@@ -2,6 +2,7 @@
 // window forms, the LDS single-pass apply and its row reduce.
 #pragma once
 
+#include "../analytical.hpp"
 #include "edge_ops.hpp"
 #include "gpu_common.hpp"
 
@@ -652,6 +653,206 @@ __global__ __launch_bounds__(1024) void kSchurFusedLds(
         }
         atomicAdd(&oc[i], v);
       }
+    }
+  }
+  __syncthreads();
+  T* row = rows + (int64_t)blockIdx.x * nc;
+  for (int i = (int)threadIdx.x; i < nc; i += (int)blockDim.x) row[i] = acc[i];
+}
+
+// ---------------------------------------------------------------------------
+// Recomputed-J form of the LDS single-pass apply (BAL (9,3,2), implicit)
+// ---------------------------------------------------------------------------
+// For the built-in BAL residual the 24 J values an edge streams in
+// kSchurFusedLds are a pure function of the accepted camera and point.
+// kBalSnapshot keeps that linearisation point per accepted step: one
+// balCameraPart row per camera (the transcendentals, once per camera) and
+// the 4-padded points of the local shard.  kSchurFusedLdsRc then rebuilds
+// [Jc, Jp] per edge with balEdgePart (J = dres/dP [dP/daa, I, .] and
+// Jp = dres/dP R, one reciprocal) instead of loading the packed groups;
+// window slices, scan, Cinv, broadcast, weighting, LDS scatter and flush are
+// kSchurFusedLds's.  Flagged windows and the long-run finishers keep using
+// the stored grad-major J.
+template <typename T>
+__global__ void kBalSnapshot(int ncam, int ptLo, int npL,
+                             const T* __restrict__ params,
+                             T* __restrict__ camAux, T* __restrict__ ptAcc) {
+  const T* pts = params + (int64_t)ncam * 9;
+  for (int64_t idx = blockIdx.x * (int64_t)kBlk + threadIdx.x;
+       idx < (int64_t)ncam + npL; idx += (int64_t)gridDim.x * kBlk) {
+    if (idx < ncam) {
+      T row[kBalCamRow];
+      balCameraPart<T>(params + idx * 9, row);
+      for (int k = 0; k < kBalCamRow; ++k) camAux[idx * kBalCamRow + k] = row[k];
+    } else {
+      const int64_t p = ptLo + (idx - ncam);
+      for (int k = 0; k < 3; ++k) ptAcc[p * 4 + k] = pts[p * 3 + k];
+      ptAcc[p * 4 + 3] = T(0);
+    }
+  }
+}
+
+// Workgroups of at most 512 threads: holding next window's indices and the
+// Cinv block across the edge arithmetic takes 164-178 VGPRs in fp64, which
+// 16 waves per CU cannot have without scratch (profiles/kernel_resources.md).
+constexpr int kLdsRcMaxThreads = 512;
+template <typename T, bool HASINFO>
+__global__ __launch_bounds__(kLdsRcMaxThreads) void kSchurFusedLdsRc(
+    int nWin, const int64_t* __restrict__ winLo,
+    const int64_t* __restrict__ winHi, const unsigned char* __restrict__ winFlag,
+    int64_t nL, const int* __restrict__ camOf, const int* __restrict__ ptOf,
+    const T* __restrict__ camAux, const T* __restrict__ ptAcc,
+    const unsigned char* __restrict__ camFixed,
+    const unsigned char* __restrict__ ptFixed,
+    const T* const* __restrict__ jSlots, const T* __restrict__ info,
+    int lossKind, T lossD2, const T* __restrict__ xPad,
+    const T* __restrict__ HllInv, T* __restrict__ temp, int nc,
+    T* __restrict__ rows) {
+  using TV = typename PackVec<T>::type;
+  constexpr int VEC = PackVec<T>::VEC;
+  constexpr int CD = 9, PD = 3, RD = 2;
+  constexpr int PP = PD * PD;
+  constexpr int RW = RD * (RD + 1) / 2;
+  constexpr int XP = PackedEdge<T, CD, PD, RD, true>::XP;
+  extern __shared__ __align__(16) unsigned char ldsRaw[];
+  T* acc = reinterpret_cast<T*>(ldsRaw);
+  for (int i = (int)threadIdx.x; i < nc; i += (int)blockDim.x) acc[i] = T(0);
+  __syncthreads();
+  const T* rBak = jSlots[2];
+  const int lane = threadIdx.x & 63;
+  const int nWave = (int)blockDim.x >> 6;
+  const int wBeg = (int)((int64_t)nWin * blockIdx.x / gridDim.x);
+  const int wEnd = (int)((int64_t)nWin * (blockIdx.x + 1) / gridDim.x);
+  // With J gone the window is a chain of dependent memory latencies: table
+  // -> ptOf/camOf -> gathers -> arithmetic -> scan -> Cinv.  The indices are
+  // therefore loaded one window ahead and the tail lanes fetch Cinv before
+  // the arithmetic, which leaves the gathers as the one exposed latency.
+  const auto loadWindow = [&](int wi, int64_t& l, int64_t& h, bool& f, int& p,
+                              int& c) {
+    l = winLo[wi];
+    h = winHi[wi];
+    f = winFlag[wi] != 0;
+    const int64_t jj = l + lane < h ? l + lane : h - 1;
+    p = ptOf[jj];
+    c = camOf[jj];
+  };
+  int w = wBeg + ((int)threadIdx.x >> 6);
+  int64_t lo = 0, hi = 0, loN = 0, hiN = 0;
+  bool flagged = false, flaggedN = false;
+  int pt = 0, cam = 0, ptN = 0, camN = 0;
+  if (w < wEnd) loadWindow(w, lo, hi, flagged, pt, cam);
+  for (; w < wEnd; w += nWave, lo = loN, hi = hiN, flagged = flaggedN,
+                   pt = ptN, cam = camN) {
+    const bool active = lo + lane < hi;
+    const int64_t j = active ? lo + lane : hi - 1;
+    const bool tail = runTailWindow(pt, lane, active, lo, hi);
+    T inv[PP];
+    if (tail && !flagged)
+      for (int k = 0; k < PP; ++k) inv[k] = HllInv[(int64_t)pt * PP + k];
+    // an edge with a fixed end has Jc = 0 or Jp = 0 (kForward): both its
+    // t_e = Jp^T W Jc x and its scatter Jc^T W Jp w are exactly zero
+    const bool live = active && !(camFixed && camFixed[cam]) &&
+                      !(ptFixed && ptFixed[pt]);
+    T jc[RD][CD], jp[RD][PD];
+    T iw[RW];
+    T lw = T(1);
+    T t[PD];
+    for (int k = 0; k < PD; ++k) t[k] = T(0);
+    TV xbuf[XP / VEC], cbuf[kBalCamRow / VEC], pbuf[4 / VEC];
+    if (live) {
+      const TV* xv4 = (const TV*)(xPad + (int64_t)cam * XP);
+#pragma unroll
+      for (int l = 0; l < XP / VEC; ++l) xbuf[l] = xv4[l];
+      const TV* cv = (const TV*)(camAux + (int64_t)cam * kBalCamRow);
+#pragma unroll
+      for (int l = 0; l < kBalCamRow / VEC; ++l) cbuf[l] = cv[l];
+      const TV* pv = (const TV*)(ptAcc + (int64_t)pt * 4);
+#pragma unroll
+      for (int l = 0; l < 4 / VEC; ++l) pbuf[l] = pv[l];
+    }
+    if (w + nWave < wEnd)
+      loadWindow(w + nWave, loN, hiN, flaggedN, ptN, camN);
+    if (live) {
+      T row[kBalCamRow], X[4];
+#pragma unroll
+      for (int k = 0; k < kBalCamRow; ++k) row[k] = cbuf[k / VEC][k % VEC];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) X[k] = pbuf[k / VEC][k % VEC];
+      const T noMeas[RD] = {T(0), T(0)};
+      T res[RD];  // unused: the accepted residual is read from rBak
+      balEdgePart<T>(row, X, noMeas, res, jc, jp);
+      T u[RD];
+#pragma unroll
+      for (int rr = 0; rr < RD; ++rr) {
+        T v = T(0);
+#pragma unroll
+        for (int i = 0; i < CD; ++i) v += jc[rr][i] * xbuf[i / VEC][i % VEC];
+        u[rr] = v;
+      }
+      if (HASINFO) {
+        for (int k = 0; k < RW; ++k) iw[k] = info[RW * j + k];
+        T wu[RD];
+        for (int i = 0; i < RD; ++i) {
+          T v = T(0);
+          for (int k = 0; k < RD; ++k) v += iw[symIdx<RD>(i, k)] * u[k];
+          wu[i] = v;
+        }
+        for (int i = 0; i < RD; ++i) u[i] = wu[i];
+      }
+      if (lossKind) {
+        T ss = T(0);
+        for (int rr = 0; rr < RD; ++rr) {
+          const T rv = rBak[(int64_t)rr * nL + j];
+          ss += rv * rv;
+        }
+        lw = lossWeight(lossKind, lossD2, ss);
+        for (int rr = 0; rr < RD; ++rr) u[rr] *= lw;
+      }
+#pragma unroll
+      for (int k = 0; k < PD; ++k) {
+        T v = T(0);
+#pragma unroll
+        for (int rr = 0; rr < RD; ++rr) v += jp[rr][k] * u[rr];
+        t[k] = v;
+      }
+    }
+    waveSegScan(pt, lane, t);
+    if (flagged) {
+      if (tail)
+        for (int k = 0; k < PD; ++k) atomicAdd(&temp[PD * pt + k], t[k]);
+      continue;
+    }
+    T wv[PD];
+    for (int k = 0; k < PD; ++k) wv[k] = T(0);
+    if (tail) cinvApply<T, PD>(inv, t, wv);
+    tailBroadcast(tail, lane, wv);
+    if (!live) continue;
+    T* oc = acc + cam * CD;
+    T u[RD];
+#pragma unroll
+    for (int rr = 0; rr < RD; ++rr) {
+      T v = T(0);
+#pragma unroll
+      for (int k = 0; k < PD; ++k) v += jp[rr][k] * wv[k];
+      u[rr] = v;
+    }
+    if (HASINFO) {
+      T wu[RD];
+      for (int i = 0; i < RD; ++i) {
+        T v = T(0);
+        for (int k = 0; k < RD; ++k) v += iw[symIdx<RD>(i, k)] * u[k];
+        wu[i] = v;
+      }
+      for (int i = 0; i < RD; ++i) u[i] = wu[i];
+    }
+    if (lossKind)
+      for (int rr = 0; rr < RD; ++rr) u[rr] *= lw;
+#pragma unroll
+    for (int i = 0; i < CD; ++i) {
+      T v = T(0);
+#pragma unroll
+      for (int rr = 0; rr < RD; ++rr) v += jc[rr][i] * u[rr];
+      atomicAdd(&oc[i], v);
     }
   }
   __syncthreads();

@@ -19,6 +19,10 @@ struct GpuKnobs {
   bool noEtxFuse = false;    // MEGBA_NO_ETXFUSE: force the separate passes
   bool schurLds = false;     // MEGBA_SCHUR_LDS: force the LDS apply if eligible
   bool noSchurLds = false;   // MEGBA_NO_SCHUR_LDS: take the LDS apply out
+  // MEGBA_SCHUR_RECOMPUTE: force the recomputed-J LDS apply if eligible (wins
+  // over MEGBA_SCHUR_LDS); MEGBA_NO_SCHUR_RECOMPUTE: take it out
+  bool schurRecompute = false;
+  bool noSchurRecompute = false;
   bool noPcgFuse = false;    // MEGBA_NO_PCG_FUSE: seven-kernel PCG body
   bool noGraph = false;      // MEGBA_NO_GRAPH: no hipGraph capture
   bool forceRccl = false;    // MEGBA_FORCE_RCCL: world-1 RCCL communicator
@@ -44,6 +48,8 @@ struct GpuKnobs {
     k.noEtxFuse = on("MEGBA_NO_ETXFUSE");
     k.schurLds = on("MEGBA_SCHUR_LDS");
     k.noSchurLds = on("MEGBA_NO_SCHUR_LDS");
+    k.schurRecompute = on("MEGBA_SCHUR_RECOMPUTE");
+    k.noSchurRecompute = on("MEGBA_NO_SCHUR_RECOMPUTE");
     k.noPcgFuse = on("MEGBA_NO_PCG_FUSE");
     k.noGraph = on("MEGBA_NO_GRAPH");
     k.forceRccl = on("MEGBA_FORCE_RCCL");
