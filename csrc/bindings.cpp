@@ -18,6 +18,7 @@
 #include "megba/lm.hpp"
 #include "megba/problem.hpp"
 #include "megba/gpu/edge_tables.hpp"  // host-only
+#include "megba/gpu/rc_tile.hpp"      // host-only
 
 #ifdef MEGBA_WITH_GPU
 #include "megba/gpu/gpu_engine.hpp"
@@ -534,6 +535,26 @@ PYBIND11_MODULE(_core, m) {
       py::arg("cam_idx"), py::arg("pt_idx"), py::arg("ncam"), py::arg("npt"),
       py::arg("rank") = 0, py::arg("world") = 1, py::arg("chunk_rows") = 256,
       py::arg("band_pts") = 0);
+
+  // Slot function of the recompute product's LDS tile (rc_tile.hpp): byte
+  // offset of 16-byte chunk `chunk` of tile row `row`; host only.
+  m.def(
+      "rc_tile_slot",
+      [](int row, int chunk) {
+        MEGBA_CHECK(row >= 0 && row < kRcTileRows, "row out of range");
+        MEGBA_CHECK(chunk >= 0 && chunk < kRcSegChunks, "chunk out of range");
+        return rcTileSlot(row, chunk);
+      },
+      py::arg("row"), py::arg("chunk"));
+  m.attr("rc_tile_bytes") = kRcTileBytes;
+  // Dynamic LDS the staged instance needs for nc accumulators of elem_bytes
+  // each and `waves` waves per workgroup.
+  m.def(
+      "rc_staged_lds_bytes",
+      [](long long nc, int elemBytes, int waves) {
+        return rcStagedLdsBytes(nc, elemBytes, waves);
+      },
+      py::arg("nc"), py::arg("elem_bytes"), py::arg("waves"));
 
 #ifdef MEGBA_WITH_GPU
   m.attr("has_gpu_support") = true;

@@ -352,13 +352,13 @@ class GpuEngine final : public Engine<T> {
       snapshotAccepted();
   }
 
-  // Camera rows and 4-padded local points of the accepted linearisation
-  // point (kBalSnapshot), read by kSchurFusedLdsRc alone.
+  // Camera part of the row table and 4-padded local points of the accepted
+  // linearisation point (kBalSnapshot), read by kSchurFusedLdsRc alone.
   void snapshotAccepted() {
     if constexpr (kBalDims)
       hipLaunchKernelGGL(kBalSnapshot<T>, dim3(gridFor((int64_t)ncam_ + npL_)),
                          dim3(kBlk), 0, stream_, ncam_, ptLo_, npL_, dParams_,
-                         dCamAux_, dPtAcc_);
+                         dCamRow_, rcCamStride(), dPtAcc_);
   }
 
   // Point the device slots at the accepted (bak) buffer set.
@@ -602,8 +602,7 @@ class GpuEngine final : public Engine<T> {
     zeroScalar();
     if (implicit_) {
       // packed accepted J + padded deltaX camera vector
-      hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk),
-                         0, stream_, ncam_, dDeltaX_, dXPad_);
+      padX(dDeltaX_, xPadDst());
       hipLaunchKernelGGL((kRhoDenomPk<T, CD, PD, RD>), dim3(gridFor(nL_)),
                          dim3(kBlk), 0, stream_, nL_, dCamOf_, dPtOf_,
                          dR_[bak], dJPk_, dXPad_, dDeltaX_ + nc_,
@@ -863,6 +862,9 @@ class GpuEngine final : public Engine<T> {
               : tuned == SchurPath::LdsRecompute ? "lds-recompute"
               : tuned == SchurPath::FusedEtx     ? "fused-etx"
                                                  : "separate");
+    if (knobs_.tuneVerbose && tuned == SchurPath::LdsRecompute)
+      fprintf(stderr, "# schur recompute gather: %s\n",
+              rcStaged_ ? "staged" : "per-lane");
     PcgPlan plan;
     plan.path = knobs_.fused ? SchurPath::OnePass : tuned;
     plan.rotatedBody = !knobs_.noPcgFuse;
@@ -978,21 +980,38 @@ class GpuEngine final : public Engine<T> {
     });
   }
   // The same for kSchurFusedLdsRc, which exists for the BAL dims only.
-  const void* schurLdsRcKernel() const {
+  // staged: the instance that gathers the camera rows through LDS tiles.
+  const void* schurLdsRcKernel(bool staged) const {
     if constexpr (kBalDims)
-      return hasInfo_ ? (const void*)kSchurFusedLdsRc<T, true>
-                      : (const void*)kSchurFusedLdsRc<T, false>;
+      return dispatchBool(hasInfo_, [&](auto infoTag) {
+        constexpr bool HI = decltype(infoTag)::value;
+        return staged ? (const void*)kSchurFusedLdsRc<T, HI, true>
+                      : (const void*)kSchurFusedLdsRc<T, HI, false>;
+      });
     return nullptr;
   }
-  void launchSchurLdsRc(size_t ldsBytes) {
+  // Dynamic LDS of kSchurFusedLdsRc: the accumulators, and for the staged
+  // instance one tile per wave behind them.
+  size_t rcLdsBytes(bool staged) const {
+    return staged ? (size_t)rcStagedLdsBytes(nc_, (int)sizeof(T),
+                                             rcThreads_ / 64)
+                  : (size_t)nc_ * sizeof(T);
+  }
+  void launchSchurLdsRc() {
+    [[maybe_unused]] const PadDst d = padDstFor(SchurPath::LdsRecompute);
     if constexpr (kBalDims)
       dispatchBool(hasInfo_, [&](auto infoTag) {
-        hipLaunchKernelGGL(
-            (kSchurFusedLdsRc<T, decltype(infoTag)::value>), dim3(numCU_),
-            dim3(rcThreads_), ldsBytes, stream_, nWin_, dWinLo_, dWinHi_,
-            dWinFlag_, nL_, dCamOf_, dPtOf_, dCamAux_, dPtAcc_, dCamFixed_,
-            dPtFixed_, (const T* const*)dJSlots_, dInfo_, lossKind_, lossD2_,
-            dXPad_, dHllInv_, dTemp_, (int)nc_, dLdsRows_);
+        dispatchBool(rcStaged_, [&](auto stagedTag) {
+          hipLaunchKernelGGL(
+              (kSchurFusedLdsRc<T, decltype(infoTag)::value,
+                                decltype(stagedTag)::value>),
+              dim3(numCU_), dim3(rcThreads_), rcLdsBytes(rcStaged_), stream_,
+              nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_, dPtOf_,
+              dCamRow_, rcCamStride(), d.p + d.off, d.stride, dPtAcc_,
+              dCamFixed_, dPtFixed_,
+              (const T* const*)dJSlots_, dInfo_, lossKind_, lossD2_, dHllInv_,
+              dTemp_, (int)nc_, dLdsRows_);
+        });
       });
   }
   // Grid of the one-wave-per-window kernels (4 waves per block).
@@ -1000,8 +1019,8 @@ class GpuEngine final : public Engine<T> {
     const int g = (nWin + 3) / 4 < 8192 ? (nWin + 3) / 4 : 8192;
     return g < 1 ? 1 : g;
   }
-  // Input vector of a product, and whether dXPad_ already holds its
-  // XP-padded copy (the rotated PCG body's kBetaPPad writes it).
+  // Input vector of a product, and whether the path's padded copy of it
+  // (padDstFor) is already written (the rotated PCG body's kBetaPPad does).
   struct XIn {
     const T* v;
     bool padReady;
@@ -1010,12 +1029,36 @@ class GpuEngine final : public Engine<T> {
   int ldsReduceGrid() const { return (int)((nc_ + 63) / 64); }
   // Grid of kBApplyDot = number of p.q partials it writes.
   int bApplyDotGrid() const { return gridFor(nc_); }
-  // Common start of the window passes: the XP-padded copy of x unless it is
-  // ready, and a zeroed temp when >64-edge runs will add partials to it.
-  void windowPrologue(XIn x) {
-    if (!x.padReady)
-      hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                         stream_, ncam_, x.v, dXPad_);
+  // Where the padded copy of a product's input goes: the XP-stride vector
+  // dXPad_, or for the staged recompute path the x columns of its camera row
+  // table.
+  struct PadDst {
+    T* p;
+    int stride, off;
+  };
+  PadDst xPadDst() const { return {dXPad_, PkJ::XP, 0}; }
+  PadDst padDstFor(SchurPath path) const {
+    if (path == SchurPath::LdsRecompute && rcStaged_)
+      return {dCamRow_, RcRow<T>::LEN, kRcXOff};
+    return xPadDst();
+  }
+  // Row stride of the recompute path's camera table: whole 64-byte-aligned
+  // rows for the staged gather; the per-lane instance keeps bare
+  // balCameraPart rows and reads x from dXPad_ (measured faster for its
+  // loads than the wide rows, profiles/r09_rc_staged_gather.md).
+  int rcCamStride() const { return rcStaged_ ? RcRow<T>::LEN : kBalCamRow; }
+  void padX(const T* x, PadDst d) {
+    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
+                       stream_, ncam_, x, d.p, d.stride, d.off);
+  }
+  // Common start of the window passes: the padded copy of x where the path
+  // reads it unless it is ready, and a zeroed temp when >64-edge runs will
+  // add partials to it.  The long-run finishers read dXPad_ on every path,
+  // so with such runs the staged recompute path fills that as well.
+  void windowPrologue(XIn x, SchurPath path) {
+    if (!x.padReady) padX(x.v, padDstFor(path));
+    if (nLongPts_ > 0 && path == SchurPath::LdsRecompute && rcStaged_)
+      padX(x.v, xPadDst());
     if (nLongPts_ > 0)
       hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
                          dim3(kBlk), 0, stream_, dTemp_ + (int64_t)ptLo_ * PD,
@@ -1087,7 +1130,7 @@ class GpuEngine final : public Engine<T> {
     // pointers; acceptForward fills them.
     if constexpr (kBalDims) {
       if (!implicit_ || customFwd_ || knobs_.noSchurRecompute) return;
-      if (hipFuncSetAttribute(schurLdsRcKernel(),
+      if (hipFuncSetAttribute(schurLdsRcKernel(false),
                               hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)need) != hipSuccess) {
         (void)hipGetLastError();
@@ -1098,14 +1141,27 @@ class GpuEngine final : public Engine<T> {
       rcThreads_ = ldsThreads_ < kLdsRcMaxThreads && knobs_.schurLdsThreads
                        ? ldsThreads_
                        : kLdsRcMaxThreads;
-      dCamAux_ = dalloc<T>((int64_t)ncam_ * kBalCamRow);
+      // the row table's pad columns are zeroed here and never written again
+      dCamRow_ = dalloc<T>((int64_t)ncam_ * RcRow<T>::LEN);
       dPtAcc_ = dalloc<T>((int64_t)npt_ * 4);
-      HIP_CHECK(hipMemsetAsync(dCamAux_, 0,
-                               (int64_t)ncam_ * kBalCamRow * sizeof(T),
+      HIP_CHECK(hipMemsetAsync(dCamRow_, 0,
+                               (int64_t)ncam_ * RcRow<T>::LEN * sizeof(T),
                                stream_));
       HIP_CHECK(hipMemsetAsync(dPtAcc_, 0, (int64_t)npt_ * 4 * sizeof(T),
                                stream_));
       rcEligible_ = true;
+      // Staged gather: the per-wave tiles must fit behind the accumulators
+      // (MEGBA_NO_RC_STAGE takes it out); otherwise the per-lane instance
+      // runs and nothing else changes.
+      const int64_t stagedNeed = (int64_t)rcLdsBytes(true);
+      if (!knobs_.noRcStage && stagedNeed <= limit) {
+        if (hipFuncSetAttribute(schurLdsRcKernel(true),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)stagedNeed) == hipSuccess)
+          rcStaged_ = true;
+        else
+          (void)hipGetLastError();
+      }
     }
   }
 
@@ -1117,10 +1173,10 @@ class GpuEngine final : public Engine<T> {
   // implicit edge from the accepted snapshot instead of reading dJPk_.
   void schurFusedLdsEcE(XIn x, T* out, bool bApplyDot = false,
                         bool recompute = false) {
-    windowPrologue(x);
+    windowPrologue(x, recompute ? SchurPath::LdsRecompute : SchurPath::Lds);
     const size_t ldsBytes = (size_t)nc_ * sizeof(T);
     if (recompute)
-      launchSchurLdsRc(ldsBytes);
+      launchSchurLdsRc();
     else
       dispatchMode([&](auto impTag, auto infoTag) {
         constexpr bool IM = decltype(impTag)::value;
@@ -1188,9 +1244,7 @@ class GpuEngine final : public Engine<T> {
     }
     // 16B-aligned padded copy of x: the per-edge camera gather becomes
     // XP/VEC vector loads instead of CD divergent scalar loads.
-    if (!x.padReady)
-      hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                         stream_, ncam_, x.v, dXPad_);
+    if (!x.padReady) padX(x.v, xPadDst());
     dispatchMode([&](auto, auto infoTag) {
       constexpr bool HI = decltype(infoTag)::value;
       const auto kernel = knobs_.etxAtomic
@@ -1249,7 +1303,8 @@ class GpuEngine final : public Engine<T> {
   // The rotated body (default; MEGBA_NO_PCG_FUSE=1 keeps the one above).
   // z and the rho partials of the current residual already exist: from the
   // kPrecondRho before the loop, or from the previous body's last kernel.
-  //   A  kBetaPPad:         rho -> slotRho(), beta, p = z + beta p, dXPad_
+  //   A  kBetaPPad:         rho -> slotRho(), beta, p = z + beta p, padded p
+  //                         (padDstFor: dXPad_ or the camera row table)
   //      product            (skips its own kPadX)
   //   B  kLdsReduceBApplyDot when eligible, else reduce .. kBApplyDot
   //   C  kUpdateXRPrecond:  alpha, rho -> slotRhoPrev(), x/xBak/xBakPrev/r,
@@ -1257,10 +1312,11 @@ class GpuEngine final : public Engine<T> {
   void pcgBodyRotated() {
     const int nbR = precondGrid();
     if (plan_->productReadsPad) {
+      const PadDst d = padDstFor(plan_->path);
       hipLaunchKernelGGL((kBetaPPad<T, CD>),
                          dim3(gridFor((int64_t)ncam_ * PkJ::XP)), dim3(kBlk),
                          0, stream_, ncam_, dZ_, dPart_, nbR, slotRhoPrev(),
-                         slotRho(), dP_, dXPad_);
+                         slotRho(), dP_, d.p, d.stride, d.off);
     } else {
       hipLaunchKernelGGL(kXpbySBeta<T>, dim3(gridFor(nc_)), dim3(kBlk), 0,
                          stream_, nc_, dZ_, dPart_, nbR, slotRhoPrev(),
@@ -1318,7 +1374,7 @@ class GpuEngine final : public Engine<T> {
   // negative, kept env-gated).
   void schurFusedEcE(XIn x, T* out) {
     HIP_CHECK(hipMemsetAsync(out, 0, nc_ * sizeof(T), stream_));
-    windowPrologue(x);
+    windowPrologue(x, SchurPath::OnePass);
     dispatchMode([&](auto impTag, auto infoTag) {
       constexpr bool IM = decltype(impTag)::value;
       constexpr bool HI = decltype(infoTag)::value;
@@ -1334,7 +1390,7 @@ class GpuEngine final : public Engine<T> {
   // w = Cinv E^T x into the 4-padded w vector, one fused window pass
   // (default path; see kEtxCinvFused).
   void etxCinv(XIn x) {
-    windowPrologue(x);
+    windowPrologue(x, SchurPath::FusedEtx);
     dispatchMode([&](auto impTag, auto infoTag) {
       constexpr bool IM = decltype(impTag)::value;
       constexpr bool HI = decltype(infoTag)::value;
@@ -1402,7 +1458,10 @@ class GpuEngine final : public Engine<T> {
   // of the accepted linearisation point that acceptForward refreshes.
   bool rcEligible_ = false;
   int rcThreads_ = kLdsRcMaxThreads;
-  T* dCamAux_{};  // [ncam_][kBalCamRow] balCameraPart rows
+  bool rcStaged_ = false;  // the LDS-staged gather instance runs
+  // [ncam_][RcRow<T>::LEN] camera row table (rc_tile.hpp): balCameraPart
+  // row, then the product's padded input x, then zeros
+  T* dCamRow_{};
   T* dPtAcc_{};   // [npt_][4] accepted points, 4-padded, global point id
   int nWin_ = 0, nFlagWins_ = 0, nLongPts_ = 0;
   int64_t* dWinLo_{};

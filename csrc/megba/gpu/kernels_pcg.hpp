@@ -166,14 +166,14 @@ __global__ void kUpdateXRAlpha(int64_t n, const double* __restrict__ partR,
 //   kUpdateXRPrecond   = kUpdateXRAlpha + kPrecondRho
 
 // beta + p-update (as kXpbySBeta) that also writes the XP-padded copy of the
-// new p in kPadX's layout, zero pad lanes included.  One thread per padded
-// element.
+// new p in kPadX's layout and to kPadX's (dst, stride, off), zero pad lanes
+// included.  One thread per padded element.
 template <typename T, int CD>
 __global__ void kBetaPPad(int ncam, const T* __restrict__ z,
                           const double* __restrict__ part, int nb,
                           const double* __restrict__ rhoPrev,
                           double* __restrict__ rhoOut, T* __restrict__ p,
-                          T* __restrict__ xPad) {
+                          T* __restrict__ dst, int stride, int off) {
   constexpr int VEC = PackVec<T>::VEC;
   constexpr int XP = (CD + VEC - 1) / VEC * VEC;
   __shared__ double sm[kBlk];
@@ -199,7 +199,7 @@ __global__ void kBetaPPad(int ncam, const T* __restrict__ z,
       pv = z[i] + beta * p[i];
       p[i] = pv;
     }
-    xPad[idx] = pv;
+    dst[c * stride + off + k] = pv;
   }
 }
 

@@ -5,6 +5,7 @@
 #include "../analytical.hpp"
 #include "edge_ops.hpp"
 #include "gpu_common.hpp"
+#include "rc_tile.hpp"
 
 namespace megba {
 namespace {
@@ -673,17 +674,32 @@ __global__ __launch_bounds__(1024) void kSchurFusedLds(
 // window slices, scan, Cinv, broadcast, weighting, LDS scatter and flush are
 // kSchurFusedLds's.  Flagged windows and the long-run finishers keep using
 // the stored grad-major J.
+//
+// Camera data lives in one row table camRow[ncam][RcRow<T>::LEN]
+// (rc_tile.hpp): kBalSnapshot writes the balCameraPart row, and the writers
+// of the padded x (kBetaPPad, kPadX) put the product's input behind it, so an
+// edge's whole camera side is one 64-byte-aligned row.  The cameras of a
+// window are all different as a rule, and a per-lane load of 16 bytes then
+// touches 64 cache lines per wave instruction.  The STAGED instance loads
+// every 64-byte segment of the window's 64 rows once, four neighbouring lanes
+// per segment, and hands each lane its own row through a wave-private LDS
+// tile behind the accumulator (one segment of the 64 rows at a time,
+// rcTileSlot's layout).  The per-lane instance keeps the two tables it had
+// (camera rows at a kBalCamRow stride, x in the XP-padded vector): on the
+// 192-byte rows its loads measured slower.  The tile is written and read by one wave only, so a
+// wavefront-scope fence orders it; the window loop holds no block barrier.
 template <typename T>
 __global__ void kBalSnapshot(int ncam, int ptLo, int npL,
                              const T* __restrict__ params,
-                             T* __restrict__ camAux, T* __restrict__ ptAcc) {
+                             T* __restrict__ camRow, int camStride,
+                             T* __restrict__ ptAcc) {
   const T* pts = params + (int64_t)ncam * 9;
   for (int64_t idx = blockIdx.x * (int64_t)kBlk + threadIdx.x;
        idx < (int64_t)ncam + npL; idx += (int64_t)gridDim.x * kBlk) {
     if (idx < ncam) {
       T row[kBalCamRow];
       balCameraPart<T>(params + idx * 9, row);
-      for (int k = 0; k < kBalCamRow; ++k) camAux[idx * kBalCamRow + k] = row[k];
+      for (int k = 0; k < kBalCamRow; ++k) camRow[idx * camStride + k] = row[k];
     } else {
       const int64_t p = ptLo + (idx - ncam);
       for (int k = 0; k < 3; ++k) ptAcc[p * 4 + k] = pts[p * 3 + k];
@@ -696,24 +712,31 @@ __global__ void kBalSnapshot(int ncam, int ptLo, int npL,
 // Cinv block across the edge arithmetic takes 164-178 VGPRs in fp64, which
 // 16 waves per CU cannot have without scratch (profiles/kernel_resources.md).
 constexpr int kLdsRcMaxThreads = 512;
-template <typename T, bool HASINFO>
+template <typename T, bool HASINFO, bool STAGED>
 __global__ __launch_bounds__(kLdsRcMaxThreads) void kSchurFusedLdsRc(
     int nWin, const int64_t* __restrict__ winLo,
     const int64_t* __restrict__ winHi, const unsigned char* __restrict__ winFlag,
     int64_t nL, const int* __restrict__ camOf, const int* __restrict__ ptOf,
-    const T* __restrict__ camAux, const T* __restrict__ ptAcc,
+    const T* __restrict__ camRow, int camStride, const T* __restrict__ xPad,
+    int xStride, const T* __restrict__ ptAcc,
     const unsigned char* __restrict__ camFixed,
     const unsigned char* __restrict__ ptFixed,
     const T* const* __restrict__ jSlots, const T* __restrict__ info,
-    int lossKind, T lossD2, const T* __restrict__ xPad,
-    const T* __restrict__ HllInv, T* __restrict__ temp, int nc,
-    T* __restrict__ rows) {
+    int lossKind, T lossD2, const T* __restrict__ HllInv,
+    T* __restrict__ temp, int nc, T* __restrict__ rows) {
   using TV = typename PackVec<T>::type;
   constexpr int VEC = PackVec<T>::VEC;
   constexpr int CD = 9, PD = 3, RD = 2;
   constexpr int PP = PD * PD;
   constexpr int RW = RD * (RD + 1) / 2;
   constexpr int XP = PackedEdge<T, CD, PD, RD, true>::XP;
+  constexpr int LEN = RcRow<T>::LEN;
+  constexpr int SEGS = RcRow<T>::SEGS;
+  // 16-byte chunks of a row that an edge consumes: camera part, then x
+  constexpr int NUSE = (kRcXOff + XP) / VEC;
+  static_assert(kRcXOff % VEC == 0 && kRcXOff >= kBalCamRow &&
+                    kRcXOff + XP <= LEN && VEC * (int)sizeof(T) == kRcChunkBytes,
+                "row layout");
   extern __shared__ __align__(16) unsigned char ldsRaw[];
   T* acc = reinterpret_cast<T*>(ldsRaw);
   for (int i = (int)threadIdx.x; i < nc; i += (int)blockDim.x) acc[i] = T(0);
@@ -721,20 +744,29 @@ __global__ __launch_bounds__(kLdsRcMaxThreads) void kSchurFusedLdsRc(
   const T* rBak = jSlots[2];
   const int lane = threadIdx.x & 63;
   const int nWave = (int)blockDim.x >> 6;
+  [[maybe_unused]] unsigned char* tile =
+      ldsRaw + rcTileOffset(nc, (int)sizeof(T)) +
+      ((int)threadIdx.x >> 6) * kRcTileBytes;
   const int wBeg = (int)((int64_t)nWin * blockIdx.x / gridDim.x);
   const int wEnd = (int)((int64_t)nWin * (blockIdx.x + 1) / gridDim.x);
   // With J gone the window is a chain of dependent memory latencies: table
   // -> ptOf/camOf -> gathers -> arithmetic -> scan -> Cinv.  The indices are
   // therefore loaded one window ahead and the tail lanes fetch Cinv before
   // the arithmetic, which leaves the gathers as the one exposed latency.
-  const auto loadWindow = [&](int wi, int64_t& l, int64_t& h, bool& f, int& p,
-                              int& c) {
+  const auto loadWindowTable = [&](int wi, int64_t& l, int64_t& h, bool& f) {
     l = winLo[wi];
     h = winHi[wi];
     f = winFlag[wi] != 0;
+  };
+  const auto loadWindowEdges = [&](int64_t l, int64_t h, int& p, int& c) {
     const int64_t jj = l + lane < h ? l + lane : h - 1;
     p = ptOf[jj];
     c = camOf[jj];
+  };
+  const auto loadWindow = [&](int wi, int64_t& l, int64_t& h, bool& f, int& p,
+                              int& c) {
+    loadWindowTable(wi, l, h, f);
+    loadWindowEdges(l, h, p, c);
   };
   int w = wBeg + ((int)threadIdx.x >> 6);
   int64_t lo = 0, hi = 0, loN = 0, hiN = 0;
@@ -758,24 +790,78 @@ __global__ __launch_bounds__(kLdsRcMaxThreads) void kSchurFusedLdsRc(
     T lw = T(1);
     T t[PD];
     for (int k = 0; k < PD; ++k) t[k] = T(0);
-    TV xbuf[XP / VEC], cbuf[kBalCamRow / VEC], pbuf[4 / VEC];
+    // rbuf: this lane's camera row in 16-byte chunks
+    TV rbuf[STAGED ? SEGS * kRcSegChunks : NUSE], pbuf[4 / VEC];
+    [[maybe_unused]] TV gbuf[STAGED ? SEGS : 1][kRcSegChunks];
+    if constexpr (STAGED) {
+      // All 64 lanes load, whatever active / live say: the clamped j gives
+      // every lane a valid camera, and a lane fetches for its neighbours.
+      // Instruction i of segment s: this lane loads chunk lane % 4 of
+      // segment s of the row of lane 16 i + lane / 4, so a lane quad reads
+      // 64 contiguous, 64-byte-aligned bytes.
+      const TV* src[kRcSegChunks];
+#pragma unroll
+      for (int i = 0; i < kRcSegChunks; ++i) {
+        const int ci = __shfl(cam, 16 * i + (lane >> 2), 64);
+        src[i] = (const TV*)(camRow + (int64_t)ci * LEN) + (lane & 3);
+      }
+#pragma unroll
+      for (int s = 0; s < SEGS; ++s)
+#pragma unroll
+        for (int i = 0; i < kRcSegChunks; ++i)
+          gbuf[s][i] = src[i][s * kRcSegChunks];
+    } else if (live) {
+      // per-lane: camera part and x from wherever the engine keeps them
+      // (camStride / xStride), as before the row table
+      const TV* xv4 = (const TV*)(xPad + (int64_t)cam * xStride);
+#pragma unroll
+      for (int l = 0; l < XP / VEC; ++l) rbuf[kRcXOff / VEC + l] = xv4[l];
+      const TV* cv = (const TV*)(camRow + (int64_t)cam * camStride);
+#pragma unroll
+      for (int l = 0; l < kBalCamRow / VEC; ++l) rbuf[l] = cv[l];
+    }
     if (live) {
-      const TV* xv4 = (const TV*)(xPad + (int64_t)cam * XP);
-#pragma unroll
-      for (int l = 0; l < XP / VEC; ++l) xbuf[l] = xv4[l];
-      const TV* cv = (const TV*)(camAux + (int64_t)cam * kBalCamRow);
-#pragma unroll
-      for (int l = 0; l < kBalCamRow / VEC; ++l) cbuf[l] = cv[l];
       const TV* pv = (const TV*)(ptAcc + (int64_t)pt * 4);
 #pragma unroll
       for (int l = 0; l < 4 / VEC; ++l) pbuf[l] = pv[l];
     }
-    if (w + nWave < wEnd)
+    // The staged instance reads the next window's table entry without a
+    // branch (clamped to the slice) and its edges after the tile rounds: the
+    // waits on the row segments then count the loads issued behind them
+    // instead of draining them, and ptOf / camOf stay in flight across the
+    // arithmetic.
+    if constexpr (STAGED)
+      loadWindowTable(w + nWave < wEnd ? w + nWave : w, loN, hiN, flaggedN);
+    else if (w + nWave < wEnd)
       loadWindow(w + nWave, loN, hiN, flaggedN, ptN, camN);
+    if constexpr (STAGED) {
+      // every load above is issued before the first tile round
+      __builtin_amdgcn_sched_barrier(0);
+      // One segment of the 64 rows at a time through the wave's tile: four
+      // 128-bit stores of what this lane fetched, four 128-bit loads of its
+      // own row.  A wave's LDS operations complete in order; the fences keep
+      // the compiler from moving them across each other.
+#pragma unroll
+      for (int s = 0; s < SEGS; ++s) {
+#pragma unroll
+        for (int i = 0; i < kRcSegChunks; ++i)
+          *(TV*)(tile + rcTileSlot(16 * i + (lane >> 2), lane & 3)) =
+              gbuf[s][i];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < kRcSegChunks; ++k)
+          rbuf[s * kRcSegChunks + k] =
+              *(const TV*)(tile + rcTileSlot(lane, k));
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
+      loadWindowEdges(loN, hiN, ptN, camN);
+    }
     if (live) {
       T row[kBalCamRow], X[4];
 #pragma unroll
-      for (int k = 0; k < kBalCamRow; ++k) row[k] = cbuf[k / VEC][k % VEC];
+      for (int k = 0; k < kBalCamRow; ++k) row[k] = rbuf[k / VEC][k % VEC];
 #pragma unroll
       for (int k = 0; k < 4; ++k) X[k] = pbuf[k / VEC][k % VEC];
       const T noMeas[RD] = {T(0), T(0)};
@@ -786,7 +872,8 @@ __global__ __launch_bounds__(kLdsRcMaxThreads) void kSchurFusedLdsRc(
       for (int rr = 0; rr < RD; ++rr) {
         T v = T(0);
 #pragma unroll
-        for (int i = 0; i < CD; ++i) v += jc[rr][i] * xbuf[i / VEC][i % VEC];
+        for (int i = 0; i < CD; ++i)
+          v += jc[rr][i] * rbuf[(kRcXOff + i) / VEC][(kRcXOff + i) % VEC];
         u[rr] = v;
       }
       if (HASINFO) {
@@ -917,17 +1004,20 @@ __global__ void kCinvPad(int nBlk, const T* __restrict__ A,
 
 // Pad the CD-stride camera vector to a 16B-aligned XP stride (one vector
 // store per camera) so the E^T x per-edge gather is XP/VEC vector loads
-// instead of CD divergent scalar loads.
+// instead of CD divergent scalar loads.  The XP values of camera c go to
+// dst + c * stride + off: (dXPad_, XP, 0) for the padded vector, and the x
+// columns of the recompute path's camera row table (stride and off whole
+// 16-byte groups).
 template <typename T, int CD>
-__global__ void kPadX(int ncam, const T* __restrict__ x,
-                      T* __restrict__ xPad) {
+__global__ void kPadX(int ncam, const T* __restrict__ x, T* __restrict__ dst,
+                      int stride, int off) {
   using TV = typename PackVec<T>::type;
   constexpr int VEC = PackVec<T>::VEC;
   constexpr int XP = (CD + VEC - 1) / VEC * VEC;
   for (int64_t c = blockIdx.x * (int64_t)kBlk + threadIdx.x; c < ncam;
        c += (int64_t)gridDim.x * kBlk) {
     const T* xc = x + c * CD;
-    TV* o = (TV*)(xPad + c * XP);
+    TV* o = (TV*)(dst + c * stride + off);
     for (int l = 0; l < XP / VEC; ++l) {
       TV v;
       for (int q = 0; q < VEC; ++q) {

@@ -23,6 +23,9 @@ struct GpuKnobs {
   // over MEGBA_SCHUR_LDS); MEGBA_NO_SCHUR_RECOMPUTE: take it out
   bool schurRecompute = false;
   bool noSchurRecompute = false;
+  // MEGBA_NO_RC_STAGE: the recompute apply gathers camera rows per lane
+  // instead of through the staged, quad-coalesced LDS tile
+  bool noRcStage = false;
   bool noPcgFuse = false;    // MEGBA_NO_PCG_FUSE: seven-kernel PCG body
   bool noGraph = false;      // MEGBA_NO_GRAPH: no hipGraph capture
   bool forceRccl = false;    // MEGBA_FORCE_RCCL: world-1 RCCL communicator
@@ -50,6 +53,7 @@ struct GpuKnobs {
     k.noSchurLds = on("MEGBA_NO_SCHUR_LDS");
     k.schurRecompute = on("MEGBA_SCHUR_RECOMPUTE");
     k.noSchurRecompute = on("MEGBA_NO_SCHUR_RECOMPUTE");
+    k.noRcStage = on("MEGBA_NO_RC_STAGE");
     k.noPcgFuse = on("MEGBA_NO_PCG_FUSE");
     k.noGraph = on("MEGBA_NO_GRAPH");
     k.forceRccl = on("MEGBA_FORCE_RCCL");
