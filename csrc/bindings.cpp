@@ -102,6 +102,42 @@ struct PyProblem {
     readMask(ptFixed, prob.npt, prob.ptFixed);
   }
 
+  // Record one kind of unary prior (kind: 0 camera parameters, 1 point,
+  // 2 camera centre).  Only "too late" is refused here; everything about the
+  // arrays is judged by build(), which knows the model the dims select.
+  std::string priorShapeErr[3];
+  void setPrior(int kind,
+                py::array_t<int, py::array::c_style | py::array::forcecast> idx,
+                py::array_t<double, py::array::c_style | py::array::forcecast>
+                    mean,
+                py::object info) {
+    MEGBA_CHECK(!engD && !engF, "priors must be set before build()");
+    PriorList& l = kind == 0 ? prob.camPrior
+                   : kind == 1 ? prob.ptPrior
+                               : prob.centerPrior;
+    const int D = kind == 0 ? prob.camDim : kind == 1 ? prob.ptDim : 3;
+    const py::ssize_t m = idx.size();
+    l.idx.assign(idx.data(), idx.data() + m);
+    l.mean.assign(mean.data(), mean.data() + mean.size());
+    l.info.clear();
+    std::string err;
+    if (idx.ndim() != 1) err = "prior idx must be one-dimensional";
+    if (mean.ndim() != 2 || mean.shape(0) != m || mean.shape(1) != D)
+      err = "prior mean must be (len(idx), " + std::to_string(D) + ")";
+    if (!info.is_none()) {
+      auto arr = py::cast<
+          py::array_t<double, py::array::c_style | py::array::forcecast>>(info);
+      const int W = D * (D + 1) / 2;
+      if (arr.ndim() != 2 || arr.shape(0) != m || arr.shape(1) != W)
+        err = "prior info must be (len(idx), " + std::to_string(W) +
+              ") packed-upper symmetric (see pack_sym)";
+      l.info.assign(arr.data(), arr.data() + arr.size());
+      // an empty list means identity: keep a malformed empty array an error
+      if (arr.size() == 0 && m > 0) err = "prior info is empty";
+    }
+    priorShapeErr[kind] = err;
+  }
+
   void build(const std::string& device, const std::string& dtype, int rank,
              int worldSize, int deviceIndex, const std::string& diff,
              const std::string& schur, const std::string& loss,
@@ -151,6 +187,8 @@ struct PyProblem {
     isDouble = dtype != "float32";
     MEGBA_CHECK(customForward.is_none() || isDouble,
                 "custom_forward requires float64");
+    for (const std::string& err : priorShapeErr) MEGBA_CHECK(err.empty(), err);
+    validatePriors(prob, !customForward.is_none());
     CustomForward<double> cf = wrapCustomForward(customForward);
     ix = buildIndex(prob, worldSize);
     if (opt.device == Device::CPU) {
@@ -457,6 +495,8 @@ PYBIND11_MODULE(_core, m) {
            py::arg("allreduce") = py::none(), py::arg("rccl_id") = py::none(),
            py::arg("custom_forward") = py::none(),
            py::arg("intrinsics") = py::none())
+      .def("set_prior", &PyProblem::setPrior, py::arg("kind"), py::arg("idx"),
+           py::arg("mean"), py::arg("info") = py::none())
       .def("solve", &PyProblem::solve, py::arg("max_iter") = 20,
            py::arg("tau") = 1e4, py::arg("epsilon1") = 1.0,
            py::arg("epsilon2") = 1e-10, py::arg("solver_max_iter") = 100,

@@ -23,6 +23,7 @@
 #include "analytical.hpp"
 #include "bal_functor.hpp"
 #include "lm.hpp"
+#include "prior.hpp"
 #include "smallmat.hpp"
 
 namespace megba {
@@ -122,10 +123,18 @@ class CpuEngine final : public Engine<T> {
     deltaX_.assign(dim_, T(0));
     deltaXBak_.assign(dim_, T(0));
     gBak_.assign(dim_, T(0));
+
+    // Unary priors.  Camera kinds are replicated (every rank adds their H/g
+    // terms after the allreduce; rank 0 alone counts their chi^2 and rho
+    // terms); point priors live on the rank that owns the point.
+    initPrior<CD>(camPr_, prob.camPrior, 0, ncam_, 0);
+    initPrior<3>(ctrPr_, prob.centerPrior, 0, ncam_, 18);
+    initPrior<PD>(ptPr_, prob.ptPrior, ptLo_, ptHi_, 0);
   }
 
   double forward() override {
     freshCur_ = true;
+    priorChi2_ = priorForward();
     if (customFwd_) return forwardCustom();
     using J = Jet<T, GW>;
     T chi2 = T(0);
@@ -166,7 +175,7 @@ class CpuEngine final : public Engine<T> {
       }
       zeroFixed(e);
     }
-    return scalarAr(chi2, 's');
+    return scalarAr(chi2 + priorChi2_, 's');
   }
 
   void buildLinearSystem() override {
@@ -265,12 +274,19 @@ class CpuEngine final : public Engine<T> {
       ar_(Hpp_.data(), Hpp_.size(), 's');
       ar_(gc, (size_t)ncam_ * CD, 's');
     }
+    // Prior terms go in after the allreduce: every rank adds the same
+    // replicated camera terms once; point terms stay on the owning rank.
+    priorAssemble();
   }
 
   void acceptForward() override {
     std::swap(rCur_, rBak_);
     std::swap(JcCur_, JcBak_);
     std::swap(JpCur_, JpBak_);
+    for (PriorSet* s : {&camPr_, &ctrPr_, &ptPr_}) {
+      std::swap(s->rCur, s->rBak);
+      std::swap(s->JCur, s->JBak);
+    }
     // After swap the accepted data is in *Bak_; rhoDenominator reads Bak_,
     // forward overwrites Cur_.
     freshCur_ = false;
@@ -440,7 +456,7 @@ class CpuEngine final : public Engine<T> {
       }
       s += lossRho(lossKind_, lossD2_, ss);
     }
-    return scalarAr(s, 's') - chi2Backup;
+    return scalarAr(s + priorRho(), 's') - chi2Backup;
   }
 
   // ---- debug access -------------------------------------------------------
@@ -477,6 +493,156 @@ class CpuEngine final : public Engine<T> {
   }
 
  private:
+  // ---- unary priors (prior.hpp) -------------------------------------------
+  // One kind's local entries; r (and the centre kind's J) are double-
+  // buffered and swapped at acceptForward exactly like the edge r/J.
+  struct PriorSet {
+    int64_t m = 0;
+    std::vector<int> idx;
+    std::vector<T> mean, info;  // [k][D], [k][D(D+1)/2] (identity if unset)
+    std::vector<T> rCur, rBak;  // [k][D]
+    std::vector<T> JCur, JBak;  // centre kind only: [k][3][6]
+  };
+
+  // Keep the entries whose vertex lies in [lo, hi).
+  template <int D>
+  void initPrior(PriorSet& s, const PriorList& l, int lo, int hi, int jw) {
+    constexpr int W = D * (D + 1) / 2;
+    for (size_t k = 0; k < l.idx.size(); ++k) {
+      const int v = l.idx[k];
+      if (v < lo || v >= hi) continue;
+      s.idx.push_back(v);
+      for (int i = 0; i < D; ++i) s.mean.push_back((T)l.mean[k * D + i]);
+      for (int i = 0; i < D; ++i)
+        for (int j = i; j < D; ++j)
+          s.info.push_back(l.info.empty() ? T(i == j)
+                                          : (T)l.info[k * W + packedIdx<D>(i, j)]);
+    }
+    s.m = (int64_t)s.idx.size();
+    s.rCur.assign((size_t)s.m * D, T(0));
+    s.rBak.assign((size_t)s.m * D, T(0));
+    s.JCur.assign((size_t)s.m * jw, T(0));
+    s.JBak.assign((size_t)s.m * jw, T(0));
+  }
+
+  // r = x - mean into the current set; returns sum r^T L r.
+  template <int D>
+  T paramPriorForward(PriorSet& s, const T* x) {
+    constexpr int W = D * (D + 1) / 2;
+    T chi = T(0);
+#pragma omp parallel for num_threads(nt_) schedule(static) \
+    reduction(+ : chi) if (s.m > 4096)
+    for (int64_t k = 0; k < s.m; ++k) {
+      T* r = &s.rCur[(size_t)k * D];
+      const T* xv = &x[(size_t)s.idx[k] * D];
+      for (int i = 0; i < D; ++i) r[i] = xv[i] - s.mean[(size_t)k * D + i];
+      chi += symQuad<T, D>(&s.info[(size_t)k * W], r);
+    }
+    return chi;
+  }
+
+  // This rank's share of the priors' chi^2 at the current parameters.
+  T priorForward() {
+    T cam = paramPriorForward<CD>(camPr_, cams_.data());
+    if constexpr (CD >= 6) {
+      PriorSet& s = ctrPr_;
+      for (int64_t k = 0; k < s.m; ++k) {
+        T C[3];
+        cameraCentre<T>(&cams_[(size_t)s.idx[k] * CD], C, &s.JCur[18 * k]);
+        T* r = &s.rCur[3 * k];
+        for (int a = 0; a < 3; ++a) r[a] = C[a] - s.mean[3 * k + a];
+        cam += symQuad<T, 3>(&s.info[6 * k], r);
+      }
+    }
+    if (rank_ != 0) cam = T(0);
+    return cam + paramPriorForward<PD>(ptPr_, pts_.data());
+  }
+
+  // H += L, g -= L r on the vertex's own block (J = I).
+  template <int D>
+  void paramPriorAssemble(const PriorSet& s, const std::vector<uint8_t>& fixed,
+                          T* H, T* g) {
+    constexpr int W = D * (D + 1) / 2;
+#pragma omp parallel for num_threads(nt_) schedule(static) if (s.m > 4096)
+    for (int64_t k = 0; k < s.m; ++k) {
+      const int v = s.idx[k];
+      if (fixed[v]) continue;
+      const T* L = &s.info[(size_t)k * W];
+      T Lr[D];
+      symApply<T, D>(L, &s.rBak[(size_t)k * D], Lr);
+      for (int i = 0; i < D; ++i) {
+        for (int j = 0; j < D; ++j)
+          H[(size_t)v * D * D + i * D + j] += L[packedIdx<D>(i, j)];
+        g[(size_t)v * D + i] -= Lr[i];
+      }
+    }
+  }
+
+  void priorAssemble() {
+    paramPriorAssemble<CD>(camPr_, camFixed_, Hpp_.data(), g_.data());
+    paramPriorAssemble<PD>(ptPr_, ptFixed_, Hll_.data(),
+                           g_.data() + (size_t)ncam_ * CD);
+    // centre kind: J^T L J on the leading 6x6 of the camera block
+    const PriorSet& s = ctrPr_;
+    for (int64_t k = 0; k < s.m; ++k) {
+      const int c = s.idx[k];
+      if (camFixed_[c]) continue;
+      const T* J = &s.JBak[18 * k];
+      const T* L = &s.info[6 * k];
+      T Lr[3];
+      symApply<T, 3>(L, &s.rBak[3 * k], Lr);
+      for (int i = 0; i < 6; ++i) {
+        T col[3] = {J[i], J[6 + i], J[12 + i]}, u[3];
+        symApply<T, 3>(L, col, u);
+        for (int j = 0; j < 6; ++j)
+          Hpp_[(size_t)c * CC + i * CD + j] +=
+              u[0] * J[j] + u[1] * J[6 + j] + u[2] * J[12 + j];
+        g_[(size_t)c * CD + i] -= J[i] * Lr[0] + J[6 + i] * Lr[1] +
+                                  J[12 + i] * Lr[2];
+      }
+    }
+  }
+
+  // sum (dx + r)^T L (dx + r) over the accepted set (J = I); a fixed
+  // vertex does not move, so its term stays the r^T L r inside chi2Backup.
+  template <int D>
+  T paramPriorRho(const PriorSet& s, const std::vector<uint8_t>& fixed,
+                  const T* dx) {
+    constexpr int W = D * (D + 1) / 2;
+    T sum = T(0);
+#pragma omp parallel for num_threads(nt_) schedule(static) \
+    reduction(+ : sum) if (s.m > 4096)
+    for (int64_t k = 0; k < s.m; ++k) {
+      const int v = s.idx[k];
+      T a[D];
+      for (int i = 0; i < D; ++i)
+        a[i] = s.rBak[(size_t)k * D + i] +
+               (fixed[v] ? T(0) : dx[(size_t)v * D + i]);
+      sum += symQuad<T, D>(&s.info[(size_t)k * W], a);
+    }
+    return sum;
+  }
+
+  T priorRho() {
+    T cam = paramPriorRho<CD>(camPr_, camFixed_, deltaX_.data());
+    const PriorSet& s = ctrPr_;
+    for (int64_t k = 0; k < s.m; ++k) {
+      const int c = s.idx[k];
+      const T* J = &s.JBak[18 * k];
+      T a[3];
+      for (int b = 0; b < 3; ++b) {
+        a[b] = s.rBak[3 * k + b];
+        if (!camFixed_[c])
+          for (int i = 0; i < 6; ++i)
+            a[b] += J[6 * b + i] * deltaX_[(size_t)c * CD + i];
+      }
+      cam += symQuad<T, 3>(&s.info[6 * k], a);
+    }
+    if (rank_ != 0) cam = T(0);
+    return cam + paramPriorRho<PD>(ptPr_, ptFixed_,
+                                   deltaX_.data() + (size_t)ncam_ * CD);
+  }
+
   double forwardCustom() {
     // Gather the GW parameter leaves + RD measurement rows as JetVectors,
     // run the user expression, repack the residual dual parts.
@@ -524,7 +690,7 @@ class CpuEngine final : public Engine<T> {
       chi2 += lossRho(lossKind_, lossD2_, ss);
       zeroFixed(e);
     }
-    return scalarAr(chi2, 's');
+    return scalarAr(chi2 + priorChi2_, 's');
   }
 
   // Fixed vertices (g2o parity, reference base_vertex.h `fixed`): their J
@@ -799,6 +965,8 @@ class CpuEngine final : public Engine<T> {
   std::vector<T> rCur_, JcCur_, JpCur_, rBak_, JcBak_, JpBak_;
   std::vector<T> Hpp_, Hll_, Hpl_, g_, HppD_, HllD_, HppInv_, HllInv_;
   std::vector<T> deltaX_, deltaXBak_, gBak_;
+  PriorSet camPr_, ctrPr_, ptPr_;  // camera parameter / centre / point priors
+  T priorChi2_ = T(0);             // this rank's prior share of the last forward
   std::vector<T> exScratch_, asmScratch_;  // per-thread reduction buffers
   int nt_ = 1;  // clamped OpenMP team size (see ctor)
 };

@@ -58,6 +58,7 @@
 #include "kernels_assemble.hpp"
 #include "kernels_forward.hpp"
 #include "kernels_pcg.hpp"
+#include "kernels_prior.hpp"
 #include "kernels_product.hpp"
 #include "knobs.hpp"
 
@@ -295,6 +296,12 @@ class GpuEngine final : public Engine<T> {
       dHplCam_ = dalloc<T>(nL_ * PkH::NG * PkH::VEC);
     }
     setupSchurLds(opt.deviceIndex);
+    // Unary priors: nothing is allocated for an empty kind.  Camera kinds
+    // are replicated; point priors go to the rank that owns the point.
+    initPrior<CD>(camPr_, prob.camPrior, 0, ncam_, 0);
+    initPrior<3>(ctrPr_, prob.centerPrior, 0, ncam_, 18);
+    initPrior<PD>(ptPr_, prob.ptPrior, ptLo_, ptHi_, 0);
+    hasPriors_ = camPr_.m + ctrPr_.m + ptPr_.m > 0;
     sync();
   }
 
@@ -339,6 +346,7 @@ class GpuEngine final : public Engine<T> {
                            dJp_[cur_], scalarPtr(), lossKind_, lossD2_,
                            dIntr_);
     }
+    if (hasPriors_) priorForward();
     return globalScalar(ncclSum);
   }
 
@@ -403,6 +411,8 @@ class GpuEngine final : public Engine<T> {
     } else {
       reduceDetAsync(dR_[cur_], dR_[cur_], nL_ * RD, ROp::SumSq, scalarPtr());
     }
+    // after the edge chi^2: reduceDetAsync overwrites the accumulator
+    if (hasPriors_) priorForward();
     return globalScalar(ncclSum);
   }
 
@@ -431,6 +441,9 @@ class GpuEngine final : public Engine<T> {
     // allreduced Hpp, Hll AND g, its site A1).
     allreduce(dHpp_, (int64_t)ncam_ * CC, ncclSum);
     allreduce(dG_, nc_, ncclSum);
+    // Prior terms go in after the allreduce: every rank adds the same
+    // replicated camera terms once; point terms stay on the owning shard.
+    if (hasPriors_) priorAssemble();
     sync();
   }
 
@@ -613,6 +626,7 @@ class GpuEngine final : public Engine<T> {
                          dR_[bak], dJc_[bak], dJp_[bak], dDeltaX_,
                          dDeltaX_ + nc_, scalarPtr(), lossKind_, lossD2_);
     }
+    if (hasPriors_) priorRho();
     return globalScalar(ncclSum) - chi2Backup;
   }
 
@@ -676,6 +690,136 @@ class GpuEngine final : public Engine<T> {
   }
 
  private:
+  // ---- unary priors (kernels_prior.hpp) -----------------------------------
+  // One kind's local entries, component-major; r and the centre kind's J are
+  // double-buffered on cur_ exactly like the edge r/J.
+  struct DevPrior {
+    int64_t m = 0;
+    int* idx{};
+    T *mean{}, *info{};  // [D][m], [D(D+1)/2][m] (identity if unset)
+    T* r[2]{};           // [D][m]
+    T* J[2]{};           // centre kind only: [18][m]
+  };
+
+  // Keep the entries whose vertex lies in [lo, hi) and upload them.
+  template <int D>
+  void initPrior(DevPrior& s, const PriorList& l, int lo, int hi, int jw) {
+    constexpr int W = D * (D + 1) / 2;
+    std::vector<size_t> keep;
+    for (size_t k = 0; k < l.idx.size(); ++k)
+      if (l.idx[k] >= lo && l.idx[k] < hi) keep.push_back(k);
+    const int64_t m = (int64_t)keep.size();
+    if (m == 0) return;
+    std::vector<int> idx(m);
+    std::vector<double> mean((size_t)m * D), info((size_t)m * W);
+    for (int64_t q = 0; q < m; ++q) {
+      const size_t k = keep[q];
+      idx[q] = l.idx[k];
+      for (int i = 0; i < D; ++i) mean[(size_t)i * m + q] = l.mean[k * D + i];
+      for (int i = 0; i < D; ++i)
+        for (int j = i; j < D; ++j)
+          info[(size_t)packedIdx<D>(i, j) * m + q] =
+              l.info.empty() ? (i == j ? 1.0 : 0.0)
+                             : l.info[k * W + packedIdx<D>(i, j)];
+    }
+    s.m = m;
+    s.idx = dalloc<int>(m);
+    HIP_CHECK(hipMemcpy(s.idx, idx.data(), m * sizeof(int),
+                        hipMemcpyHostToDevice));
+    s.mean = dalloc<T>(m * D);
+    s.info = dalloc<T>(m * W);
+    upCast(s.mean, mean.data(), m * D);
+    upCast(s.info, info.data(), m * W);
+    for (int b = 0; b < 2; ++b) {
+      s.r[b] = dalloc<T>(m * D);
+      HIP_CHECK(hipMemsetAsync(s.r[b], 0, m * D * sizeof(T), stream_));
+      if (jw > 0) {
+        s.J[b] = dalloc<T>(m * jw);
+        HIP_CHECK(hipMemsetAsync(s.J[b], 0, m * jw * sizeof(T), stream_));
+      }
+    }
+  }
+
+  // Grid of the kernels that end in one atomicAdd per block on the scalar
+  // accumulator: capped, so a prior on every point of a Venice-sized
+  // problem queues ~1e3 same-address atomics, not one per 256 points (the
+  // uncapped forward took 55 us for 76 MB; the grid-stride loops cover the
+  // rest).
+  static int priorRedGrid(int64_t m) {
+    const int g = gridFor(m);
+    return g < 1024 ? g : 1024;
+  }
+
+  // The camera kinds are replicated: rank 0 alone counts their scalars.
+  double* camPriorAcc() { return rank_ == 0 ? scalarPtr() : nullptr; }
+
+  // r (and the centre J) at the current parameters into the current set;
+  // adds this rank's share of sum r^T L r to the scalar accumulator.
+  void priorForward() {
+    if (camPr_.m > 0)
+      hipLaunchKernelGGL((kPriorParamForward<T, CD>), dim3(priorRedGrid(camPr_.m)),
+                         dim3(kBlk), 0, stream_, camPr_.m, camPr_.idx,
+                         dParams_, camPr_.mean, camPr_.info, camPr_.r[cur_],
+                         camPriorAcc());
+    if constexpr (CD >= 6) {
+      if (ctrPr_.m > 0)
+        hipLaunchKernelGGL((kPriorCentreForward<T, CD>),
+                           dim3(priorRedGrid(ctrPr_.m)), dim3(kBlk), 0, stream_,
+                           ctrPr_.m, ctrPr_.idx, dParams_, ctrPr_.mean,
+                           ctrPr_.info, ctrPr_.r[cur_], ctrPr_.J[cur_],
+                           camPriorAcc());
+    }
+    if (ptPr_.m > 0)
+      hipLaunchKernelGGL((kPriorParamForward<T, PD>), dim3(priorRedGrid(ptPr_.m)),
+                         dim3(kBlk), 0, stream_, ptPr_.m, ptPr_.idx,
+                         dParams_ + nc_, ptPr_.mean, ptPr_.info, ptPr_.r[cur_],
+                         scalarPtr());
+  }
+
+  // J^T L J and -J^T L r of the accepted set onto the vertices' own blocks.
+  void priorAssemble() {
+    const int bak = cur_ ^ 1;
+    if (camPr_.m > 0)
+      hipLaunchKernelGGL((kPriorParamAssemble<T, CD, true>),
+                         dim3(gridFor(camPr_.m * CD)), dim3(kBlk), 0, stream_,
+                         camPr_.m, camPr_.idx, camPr_.info, camPr_.r[bak],
+                         dCamFixed_, dHpp_, dG_);
+    if constexpr (CD >= 6) {
+      if (ctrPr_.m > 0)
+        hipLaunchKernelGGL((kPriorCentreAssemble<T, CD>),
+                           dim3(gridFor(ctrPr_.m * 6)), dim3(kBlk), 0, stream_,
+                           ctrPr_.m, ctrPr_.idx, ctrPr_.info, ctrPr_.r[bak],
+                           ctrPr_.J[bak], dCamFixed_, dHpp_, dG_);
+    }
+    if (ptPr_.m > 0)
+      hipLaunchKernelGGL((kPriorParamAssemble<T, PD, false>),
+                         dim3(gridFor(ptPr_.m)), dim3(kBlk), 0, stream_,
+                         ptPr_.m, ptPr_.idx, ptPr_.info, ptPr_.r[bak],
+                         dPtFixed_, dHll_, dG_ + nc_);
+  }
+
+  // The priors' share of the gain-ratio model, from the accepted set.
+  void priorRho() {
+    const int bak = cur_ ^ 1;
+    if (camPr_.m > 0)
+      hipLaunchKernelGGL((kPriorParamRho<T, CD>), dim3(priorRedGrid(camPr_.m)),
+                         dim3(kBlk), 0, stream_, camPr_.m, camPr_.idx,
+                         camPr_.info, camPr_.r[bak], dCamFixed_, dDeltaX_,
+                         camPriorAcc());
+    if constexpr (CD >= 6) {
+      if (ctrPr_.m > 0)
+        hipLaunchKernelGGL((kPriorCentreRho<T, CD>), dim3(priorRedGrid(ctrPr_.m)),
+                           dim3(kBlk), 0, stream_, ctrPr_.m, ctrPr_.idx,
+                           ctrPr_.info, ctrPr_.r[bak], ctrPr_.J[bak],
+                           dCamFixed_, dDeltaX_, camPriorAcc());
+    }
+    if (ptPr_.m > 0)
+      hipLaunchKernelGGL((kPriorParamRho<T, PD>), dim3(priorRedGrid(ptPr_.m)),
+                         dim3(kBlk), 0, stream_, ptPr_.m, ptPr_.idx,
+                         ptPr_.info, ptPr_.r[bak], dPtFixed_, dDeltaX_ + nc_,
+                         scalarPtr());
+  }
+
   bool weighted() const { return hasInfo_ || lossKind_ != 0; }
   int slabWidth() const {
     // must match SlabLayout<CD, PD, RD, EXPL, weighted()>::SW
@@ -1469,6 +1613,8 @@ class GpuEngine final : public Engine<T> {
   unsigned char* dWinFlag_{};
   int* dFlagWins_{};
   int* dLongPts_{};
+  DevPrior camPr_, ctrPr_, ptPr_;  // camera parameter / centre / point priors
+  bool hasPriors_ = false;
   int cur_ = 0;
   bool freshCur_ = false;  // current r/J buffers hold the last forward()
   int nChunks_ = 0;

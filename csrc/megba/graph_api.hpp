@@ -91,6 +91,49 @@ struct ReprojectionEdge {
   }
 };
 
+// Gaussian unary priors (soft constraints, prior.hpp): one vertex, a
+// measurement and an optional information matrix, packed upper-triangular
+// row by row (D(D+1)/2 values; unset = identity).  At most one prior of a
+// kind per vertex.
+struct PriorEdgeBase {
+  BaseVertex* vertex = nullptr;
+  std::vector<double> measurement;
+  std::vector<double> information;  // empty = identity
+
+ protected:
+  void attach(BaseVertex* v, VertexKind kind) {
+    MEGBA_CHECK(v != nullptr, "appendVertex(nullptr)");
+    MEGBA_CHECK(v->kind == kind, "prior edge on the wrong vertex kind");
+    MEGBA_CHECK(vertex == nullptr, "a prior edge has exactly one vertex");
+    vertex = v;
+  }
+};
+
+template <typename Derived, VertexKind KIND>
+struct PriorEdge : PriorEdgeBase {
+  Derived& appendVertex(BaseVertex* v) {
+    attach(v, KIND);
+    return static_cast<Derived&>(*this);
+  }
+  Derived& setMeasurement(const std::vector<double>& m) {
+    measurement = m;
+    return static_cast<Derived&>(*this);
+  }
+  Derived& setInformation(const std::vector<double>& packedUpper) {
+    information = packedUpper;
+    return static_cast<Derived&>(*this);
+  }
+};
+
+// r = camera parameters - measurement (camDim values)
+struct CameraPriorEdge : PriorEdge<CameraPriorEdge, VertexKind::CAMERA> {};
+// r = point - measurement (ground control point)
+struct PointPriorEdge : PriorEdge<PointPriorEdge, VertexKind::POINT> {};
+// r = C(camera) - measurement, C = -R(aa)^T t (GPS position); built-in BAL
+// residuals only
+struct CameraCenterPriorEdge
+    : PriorEdge<CameraCenterPriorEdge, VertexKind::CAMERA> {};
+
 class GraphProblem {
  public:
   // Vertices are owned by the caller and must outlive the problem; the
@@ -114,6 +157,13 @@ class GraphProblem {
     if (e.pt->slot < 0) appendVertex(e.pt);
     edges_.push_back(e);
   }
+  // Unary priors sit next to the reprojection edges; a problem still needs
+  // at least one reprojection edge.
+  void appendEdge(const CameraPriorEdge& e) { appendPrior(e, camPriors_); }
+  void appendEdge(const PointPriorEdge& e) { appendPrior(e, ptPriors_); }
+  void appendEdge(const CameraCenterPriorEdge& e) {
+    appendPrior(e, centerPriors_);
+  }
   int64_t numEdges() const { return (int64_t)edges_.size(); }
   int numVertices() const { return (int)(cams_.size() + pts_.size()); }
 
@@ -133,6 +183,7 @@ class GraphProblem {
     opt.camDim = prob.camDim;
     opt.ptDim = prob.ptDim;
     opt.resDim = prob.resDim;
+    validatePriors(prob, (bool)customForward_);
     ProblemIndex ix = buildIndex(prob, opt.worldSize);
     std::unique_ptr<Engine<double>> eng;
     if (opt.device == Device::CPU) {
@@ -198,11 +249,46 @@ class GraphProblem {
       for (int i = 0; i < p.ncam; ++i) p.camFixed[i] = cams_[i]->fixed;
       for (int i = 0; i < p.npt; ++i) p.ptFixed[i] = pts_[i]->fixed;
     }
+    packPriors(camPriors_, p.camDim, p.camPrior);
+    packPriors(ptPriors_, 3, p.ptPrior);
+    packPriors(centerPriors_, 3, p.centerPrior);
     return p;
+  }
+
+  void appendPrior(const PriorEdgeBase& e, std::vector<PriorEdgeBase>& list) {
+    MEGBA_CHECK(e.vertex != nullptr, "a prior edge needs its vertex");
+    if (e.vertex->slot < 0) appendVertex(e.vertex);
+    list.push_back(e);
+  }
+
+  // Edge list -> PriorList; unweighted edges get identity once any edge of
+  // the kind carries information.  Sizes are judged by validatePriors.
+  static void packPriors(const std::vector<PriorEdgeBase>& edges, int dim,
+                         PriorList& out) {
+    bool anyInfo = false;
+    for (const auto& e : edges) anyInfo |= !e.information.empty();
+    for (const auto& e : edges) {
+      MEGBA_CHECK((int)e.measurement.size() == dim,
+                  "prior measurement has the wrong dimension");
+      out.idx.push_back(e.vertex->slot);
+      out.mean.insert(out.mean.end(), e.measurement.begin(),
+                      e.measurement.end());
+      if (!anyInfo) continue;
+      if (!e.information.empty()) {
+        MEGBA_CHECK((int)e.information.size() == dim * (dim + 1) / 2,
+                    "prior information must be packed-upper D*(D+1)/2");
+        out.info.insert(out.info.end(), e.information.begin(),
+                        e.information.end());
+      } else {
+        for (int i = 0; i < dim; ++i)
+          for (int j = i; j < dim; ++j) out.info.push_back(i == j ? 1.0 : 0.0);
+      }
+    }
   }
 
   std::vector<BaseVertex*> cams_, pts_;
   std::vector<ReprojectionEdge> edges_;
+  std::vector<PriorEdgeBase> camPriors_, ptPriors_, centerPriors_;
   CustomForward<double> customForward_;
 };
 

@@ -14,7 +14,9 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "common.hpp"
@@ -25,6 +27,19 @@ namespace megba {
 // Block dims are carried here (default BAL 9/3/2); the reference's
 // runtime-dim analogue is ProblemOption.N + per-kernel cameraDim/pointDim/
 // resDim arguments (include/common.h:27-46, build_linear_system.cu:48-146).
+// One kind of Gaussian unary prior (prior.hpp): a sparse list over vertices,
+// at most one entry per vertex.  D = camDim (camera parameter prior), ptDim
+// (point prior) or 3 (camera-centre prior).
+struct PriorList {
+  std::vector<int> idx;      // m vertex ids
+  std::vector<double> mean;  // m*D ([entry][D])
+  // optional m * D*(D+1)/2 packed-upper symmetric information matrices;
+  // empty = identity.  Positive semi-definiteness beyond a non-negative
+  // diagonal is the caller's responsibility.
+  std::vector<double> info;
+  bool empty() const { return idx.empty(); }
+};
+
 struct BAProblemHost {
   int ncam = 0;
   int npt = 0;
@@ -42,7 +57,54 @@ struct BAProblemHost {
   std::vector<double> info;
   std::vector<uint8_t> camFixed;  // optional ncam (g2o-style fixed vertices)
   std::vector<uint8_t> ptFixed;   // optional npt
+  // optional soft unary constraints (beyond the reference)
+  PriorList camPrior;     // r = cam[c] - mean
+  PriorList ptPrior;      // r = pt[p] - mean (ground control points)
+  PriorList centerPrior;  // r = C(cam[c]) - centre (GPS), BAL cameras only
+  bool hasPriors() const {
+    return !camPrior.empty() || !ptPrior.empty() || !centerPrior.empty();
+  }
 };
+
+// Reject malformed prior lists.  `customForward`: the problem is solved with
+// a user-defined residual, whose camera parametrisation is unknown.
+inline void validatePriors(const BAProblemHost& p, bool customForward) {
+  const auto check = [](const PriorList& l, int nVert, int D,
+                        const std::string& what) {
+    const size_t m = l.idx.size();
+    const size_t W = (size_t)D * (D + 1) / 2;
+    MEGBA_CHECK(l.mean.size() == m * D,
+                what + " prior: mean must be (m, " + std::to_string(D) + ")");
+    MEGBA_CHECK(l.info.empty() || l.info.size() == m * W,
+                what + " prior: info must be (m, " + std::to_string(W) +
+                    ") packed-upper symmetric");
+    std::vector<char> seen((size_t)nVert, 0);
+    for (size_t k = 0; k < m; ++k) {
+      const int v = l.idx[k];
+      MEGBA_CHECK(v >= 0 && v < nVert, what + " prior: index out of range");
+      MEGBA_CHECK(!seen[v], what + " prior: duplicate index");
+      seen[v] = 1;
+    }
+    for (const double x : l.mean)
+      MEGBA_CHECK(std::isfinite(x), what + " prior: non-finite mean");
+    for (const double x : l.info)
+      MEGBA_CHECK(std::isfinite(x), what + " prior: non-finite info");
+    if (!l.info.empty())
+      for (size_t k = 0; k < m; ++k)
+        for (int i = 0; i < D; ++i)
+          MEGBA_CHECK(l.info[k * W + (size_t)(i * D - i * (i - 1) / 2)] >= 0.0,
+                      what + " prior: negative diagonal in info");
+  };
+  check(p.camPrior, p.ncam, p.camDim, "camera");
+  check(p.ptPrior, p.npt, p.ptDim, "point");
+  check(p.centerPrior, p.ncam, 3, "camera-centre");
+  MEGBA_CHECK(p.centerPrior.empty() ||
+                  (!customForward && (p.camDim == 9 || p.camDim == 6) &&
+                   p.ptDim == 3 && p.resDim == 2),
+              "camera-centre prior needs the built-in BAL residual ((9,3,2) "
+              "or (6,3,2), no custom forward): params 0..5 must be "
+              "angle-axis and t");
+}
 
 struct ProblemIndex {
   int ncam = 0, npt = 0;

@@ -7,10 +7,11 @@ hand-written HIP kernels for the fused autodiff forward pass, Hessian
 assembly, block inverses and the distributed PCG, with RCCL collectives
 over xGMI (one process per GPU).
 """
-from .problem import BAProblem, load_bal, save_bal  # noqa: F401
+from .problem import BAProblem, load_bal, save_bal, pack_sym  # noqa: F401
 from .synth import synthesize_bal  # noqa: F401
 from .graph import (  # noqa: F401
-    GraphProblem, CameraVertex, PointVertex, ReprojectionEdge)
+    GraphProblem, CameraVertex, PointVertex, ReprojectionEdge,
+    CameraPriorEdge, PointPriorEdge, CameraCenterPriorEdge)
 
 __version__ = "0.1.0"
 

@@ -12,7 +12,7 @@ vertices and edges, `solve()`, then read each vertex's `.estimation`
 """
 import numpy as np
 
-from .problem import BAProblem
+from .problem import BAProblem, pack_sym
 
 CAMERA = 0
 POINT = 1
@@ -70,6 +70,63 @@ class ReprojectionEdge:
         return self
 
 
+class _PriorEdge:
+    """A Gaussian unary prior: one vertex, a measurement of dimension D and
+    an optional DxD information matrix, given full or packed-upper
+    (D*(D+1)/2 values); None = identity.  At most one prior of a kind per
+    vertex."""
+
+    _kind = None  # vertex kind the edge attaches to
+
+    def __init__(self, measurement, information=None):
+        self.measurement = np.asarray(measurement,
+                                      dtype=np.float64).reshape(-1).copy()
+        d = self.measurement.size
+        if information is not None:
+            information = np.asarray(information, dtype=np.float64)
+            if information.shape == (d, d):
+                information = pack_sym(information)
+            information = information.reshape(-1)
+            if information.size != d * (d + 1) // 2:
+                raise ValueError("information must be (D, D) or packed-upper "
+                                 "D*(D+1)/2 values")
+        self.information = information
+        self.vertices = []
+
+    def append_vertex(self, v):
+        if not isinstance(v, BaseVertex):
+            raise TypeError("append_vertex expects a BaseVertex")
+        if v.kind != self._kind:
+            raise ValueError(f"{type(self).__name__} attaches to a "
+                             f"{'Camera' if self._kind == CAMERA else 'Point'}"
+                             "Vertex")
+        if self.vertices:
+            raise ValueError("a prior edge has exactly one vertex")
+        self.vertices.append(v)
+        return self
+
+
+class CameraPriorEdge(_PriorEdge):
+    """r = camera parameters - measurement (camDim values)."""
+    _kind = CAMERA
+
+
+class PointPriorEdge(_PriorEdge):
+    """r = point - measurement (ground control point)."""
+    _kind = POINT
+
+
+class CameraCenterPriorEdge(_PriorEdge):
+    """r = C(camera) - measurement, C = -R(aa)^T t (GPS position); built-in
+    BAL residuals only."""
+    _kind = CAMERA
+
+    def __init__(self, measurement, information=None):
+        super().__init__(measurement, information)
+        if self.measurement.size != 3:
+            raise ValueError("camera centre measurement must be 3-d")
+
+
 class GraphProblem:
     """g2o-style problem graph.  append_vertex / append_edge / solve;
     after solve() every vertex's .estimation holds the optimized value."""
@@ -78,6 +135,9 @@ class GraphProblem:
         self._cams = []
         self._pts = []
         self._edges = []
+        # unary prior edges by BAProblem setter name
+        self._priors = {"set_camera_prior": [], "set_point_prior": [],
+                        "set_camera_center_prior": []}
 
     def append_vertex(self, v):
         if not isinstance(v, BaseVertex):
@@ -93,6 +153,17 @@ class GraphProblem:
         return self
 
     def append_edge(self, e):
+        if isinstance(e, _PriorEdge):
+            if len(e.vertices) != 1:
+                raise ValueError("a prior edge needs its vertex")
+            if e.vertices[0]._slot is None:
+                self.append_vertex(e.vertices[0])
+            setter = ("set_camera_center_prior"
+                      if isinstance(e, CameraCenterPriorEdge)
+                      else "set_camera_prior" if e._kind == CAMERA
+                      else "set_point_prior")
+            self._priors[setter].append(e)
+            return self
         kinds = sorted(v.kind for v in e.vertices)
         if kinds != [CAMERA, POINT]:
             raise ValueError("edge must connect exactly one CameraVertex "
@@ -141,7 +212,21 @@ class GraphProblem:
             kw["cam_fixed"] = cam_fixed
         if pt_fixed.any():
             kw["pt_fixed"] = pt_fixed
-        return BAProblem(cams, pts, ci, pi, meas, info=info, **kw)
+        prob = BAProblem(cams, pts, ci, pi, meas, info=info, **kw)
+        for setter, edges in self._priors.items():
+            if not edges:
+                continue
+            idx = np.array([e.vertices[0]._slot for e in edges],
+                           dtype=np.int32)
+            mean = np.stack([e.measurement for e in edges])
+            pinfo = None
+            if any(e.information is not None for e in edges):
+                d = mean.shape[1]
+                eye = pack_sym(np.eye(d))  # default for unweighted priors
+                pinfo = np.stack([eye if e.information is None
+                                  else e.information for e in edges])
+            getattr(prob, setter)(idx, mean, pinfo)
+        return prob
 
     def solve(self, device="cpu", dtype="float64", diff="auto",
               schur="explicit", loss="none", loss_delta=1.0,

@@ -44,6 +44,38 @@ class BAProblem:
                                    self.pt_idx, self.meas, self.info, cf, pf)
         self._built = False
 
+    # -- Gaussian unary priors (soft constraints) ---------------------------
+    def _set_prior(self, kind, idx, mean, info):
+        if self._built:
+            raise RuntimeError("megba: priors must be set before build()")
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        if info is not None:
+            info = np.ascontiguousarray(info, dtype=np.float64)
+        self._core.set_prior(kind, idx, mean, info)
+        return self
+
+    def set_camera_prior(self, idx, mean, info=None):
+        """Soft constraint r = cams[idx] - mean on whole camera blocks.
+        idx: (m,) camera ids, each at most once; mean: (m, camDim);
+        info: optional (m, camDim*(camDim+1)/2) packed-upper symmetric
+        information matrices (see pack_sym), None = identity.  Adds
+        r^T info r to chi^2; no robust loss.  Arrays are checked by build().
+        """
+        return self._set_prior(0, idx, mean, info)
+
+    def set_point_prior(self, idx, mean, info=None):
+        """Soft constraint r = pts[idx] - mean (ground control points).
+        mean: (m, 3); info: optional (m, 6) packed-upper symmetric."""
+        return self._set_prior(1, idx, mean, info)
+
+    def set_camera_center_prior(self, idx, center, info=None):
+        """Soft constraint r = C(cams[idx]) - center on the camera centre
+        C = -R(aa)^T t (GPS positions).  Built-in BAL residuals only
+        ((ncam, 9) or (ncam, 6) cameras, no custom_forward).
+        center: (m, 3); info: optional (m, 6) packed-upper symmetric."""
+        return self._set_prior(2, idx, center, info)
+
     # -- build -------------------------------------------------------------
     def build(self, device="cpu", dtype="float64", rank=0, world_size=1,
               device_index=0, diff="auto", schur="explicit", loss="none",
@@ -88,6 +120,17 @@ class BAProblem:
         every rank must call it (the point shards are merged with an
         allreduce)."""
         return self._core.get_params()
+
+
+def pack_sym(M):
+    """Pack full symmetric matrices (..., D, D) into the packed-upper
+    row-major form (..., D*(D+1)/2) the `info` arguments take
+    (D=2: [m00, m01, m11])."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.ndim < 2 or M.shape[-1] != M.shape[-2]:
+        raise ValueError("pack_sym expects (..., D, D)")
+    iu = np.triu_indices(M.shape[-1])
+    return np.ascontiguousarray(M[..., iu[0], iu[1]])
 
 
 def load_bal(path):
