@@ -494,153 +494,98 @@ class CpuEngine final : public Engine<T> {
 
  private:
   // ---- unary priors (prior.hpp) -------------------------------------------
-  // One kind's local entries; r (and the centre kind's J) are double-
-  // buffered and swapped at acceptForward exactly like the edge r/J.
+  // One kind's local entries in the layout of prior.hpp; r (and the centre
+  // kind's J) are double-buffered and swapped at acceptForward exactly like
+  // the edge r/J.
   struct PriorSet {
     int64_t m = 0;
     std::vector<int> idx;
-    std::vector<T> mean, info;  // [k][D], [k][D(D+1)/2] (identity if unset)
-    std::vector<T> rCur, rBak;  // [k][D]
-    std::vector<T> JCur, JBak;  // centre kind only: [k][3][6]
+    std::vector<T> mean, info;  // identity information if the list has none
+    std::vector<T> rCur, rBak;
+    std::vector<T> JCur, JBak;  // centre kind only
+    PriorView<T> view(bool accepted) {
+      std::vector<T>& J = accepted ? JBak : JCur;
+      return {m, idx.data(), mean.data(), info.data(),
+              (accepted ? rBak : rCur).data(), J.empty() ? nullptr : J.data()};
+    }
   };
 
   // Keep the entries whose vertex lies in [lo, hi).
   template <int D>
   void initPrior(PriorSet& s, const PriorList& l, int lo, int hi, int jw) {
-    constexpr int W = D * (D + 1) / 2;
-    for (size_t k = 0; k < l.idx.size(); ++k) {
-      const int v = l.idx[k];
-      if (v < lo || v >= hi) continue;
-      s.idx.push_back(v);
-      for (int i = 0; i < D; ++i) s.mean.push_back((T)l.mean[k * D + i]);
-      for (int i = 0; i < D; ++i)
-        for (int j = i; j < D; ++j)
-          s.info.push_back(l.info.empty() ? T(i == j)
-                                          : (T)l.info[k * W + packedIdx<D>(i, j)]);
-    }
-    s.m = (int64_t)s.idx.size();
+    PackedPrior h = packPriorList<D>(l, lo, hi);
+    s.m = h.m;
+    s.idx = std::move(h.idx);
+    s.mean.assign(h.mean.begin(), h.mean.end());
+    s.info.assign(h.info.begin(), h.info.end());
     s.rCur.assign((size_t)s.m * D, T(0));
     s.rBak.assign((size_t)s.m * D, T(0));
     s.JCur.assign((size_t)s.m * jw, T(0));
     s.JBak.assign((size_t)s.m * jw, T(0));
   }
 
-  // r = x - mean into the current set; returns sum r^T L r.
-  template <int D>
-  T paramPriorForward(PriorSet& s, const T* x) {
-    constexpr int W = D * (D + 1) / 2;
+  // r (and J) at the parameters x into the current set; returns sum r^T L r.
+  template <typename Kind>
+  T priorKindForward(PriorSet& s, const T* x) {
+    const PriorView<T> p = s.view(false);
     T chi = T(0);
 #pragma omp parallel for num_threads(nt_) schedule(static) \
-    reduction(+ : chi) if (s.m > 4096)
-    for (int64_t k = 0; k < s.m; ++k) {
-      T* r = &s.rCur[(size_t)k * D];
-      const T* xv = &x[(size_t)s.idx[k] * D];
-      for (int i = 0; i < D; ++i) r[i] = xv[i] - s.mean[(size_t)k * D + i];
-      chi += symQuad<T, D>(&s.info[(size_t)k * W], r);
-    }
+    reduction(+ : chi) if (p.m > 4096)
+    for (int64_t k = 0; k < p.m; ++k) chi += priorEvaluate<Kind>(p, k, x);
     return chi;
   }
 
   // This rank's share of the priors' chi^2 at the current parameters.
   T priorForward() {
-    T cam = paramPriorForward<CD>(camPr_, cams_.data());
-    if constexpr (CD >= 6) {
-      PriorSet& s = ctrPr_;
-      for (int64_t k = 0; k < s.m; ++k) {
-        T C[3];
-        cameraCentre<T>(&cams_[(size_t)s.idx[k] * CD], C, &s.JCur[18 * k]);
-        T* r = &s.rCur[3 * k];
-        for (int a = 0; a < 3; ++a) r[a] = C[a] - s.mean[3 * k + a];
-        cam += symQuad<T, 3>(&s.info[6 * k], r);
-      }
-    }
+    T cam = priorKindForward<ParamKind<CD>>(camPr_, cams_.data());
+    if constexpr (CD >= 6)
+      cam += priorKindForward<CentreKind<CD>>(ctrPr_, cams_.data());
     if (rank_ != 0) cam = T(0);
-    return cam + paramPriorForward<PD>(ptPr_, pts_.data());
+    return cam + priorKindForward<ParamKind<PD>>(ptPr_, pts_.data());
   }
 
-  // H += L, g -= L r on the vertex's own block (J = I).
-  template <int D>
-  void paramPriorAssemble(const PriorSet& s, const std::vector<uint8_t>& fixed,
-                          T* H, T* g) {
-    constexpr int W = D * (D + 1) / 2;
-#pragma omp parallel for num_threads(nt_) schedule(static) if (s.m > 4096)
-    for (int64_t k = 0; k < s.m; ++k) {
-      const int v = s.idx[k];
-      if (fixed[v]) continue;
-      const T* L = &s.info[(size_t)k * W];
-      T Lr[D];
-      symApply<T, D>(L, &s.rBak[(size_t)k * D], Lr);
-      for (int i = 0; i < D; ++i) {
-        for (int j = 0; j < D; ++j)
-          H[(size_t)v * D * D + i * D + j] += L[packedIdx<D>(i, j)];
-        g[(size_t)v * D + i] -= Lr[i];
-      }
+  // J^T L J and -J^T L r of the accepted set onto the vertices' own blocks.
+  template <typename Kind>
+  void priorKindAssemble(PriorSet& s, const std::vector<uint8_t>& fixed, T* H,
+                         T* g) {
+    const PriorView<T> p = s.view(true);
+#pragma omp parallel for num_threads(nt_) schedule(static) if (p.m > 4096)
+    for (int64_t k = 0; k < p.m; ++k) {
+      if (fixed[p.idx[k]]) continue;
+      for (int i = 0; i < Kind::ROWS; ++i)
+        priorAssembleRow<Kind>(p, k, i, H, g);
     }
   }
 
   void priorAssemble() {
-    paramPriorAssemble<CD>(camPr_, camFixed_, Hpp_.data(), g_.data());
-    paramPriorAssemble<PD>(ptPr_, ptFixed_, Hll_.data(),
-                           g_.data() + (size_t)ncam_ * CD);
-    // centre kind: J^T L J on the leading 6x6 of the camera block
-    const PriorSet& s = ctrPr_;
-    for (int64_t k = 0; k < s.m; ++k) {
-      const int c = s.idx[k];
-      if (camFixed_[c]) continue;
-      const T* J = &s.JBak[18 * k];
-      const T* L = &s.info[6 * k];
-      T Lr[3];
-      symApply<T, 3>(L, &s.rBak[3 * k], Lr);
-      for (int i = 0; i < 6; ++i) {
-        T col[3] = {J[i], J[6 + i], J[12 + i]}, u[3];
-        symApply<T, 3>(L, col, u);
-        for (int j = 0; j < 6; ++j)
-          Hpp_[(size_t)c * CC + i * CD + j] +=
-              u[0] * J[j] + u[1] * J[6 + j] + u[2] * J[12 + j];
-        g_[(size_t)c * CD + i] -= J[i] * Lr[0] + J[6 + i] * Lr[1] +
-                                  J[12 + i] * Lr[2];
-      }
-    }
+    T* gp = g_.data() + (size_t)ncam_ * CD;
+    priorKindAssemble<ParamKind<CD>>(camPr_, camFixed_, Hpp_.data(), g_.data());
+    if constexpr (CD >= 6)
+      priorKindAssemble<CentreKind<CD>>(ctrPr_, camFixed_, Hpp_.data(),
+                                        g_.data());
+    priorKindAssemble<ParamKind<PD>>(ptPr_, ptFixed_, Hll_.data(), gp);
   }
 
-  // sum (dx + r)^T L (dx + r) over the accepted set (J = I); a fixed
-  // vertex does not move, so its term stays the r^T L r inside chi2Backup.
-  template <int D>
-  T paramPriorRho(const PriorSet& s, const std::vector<uint8_t>& fixed,
-                  const T* dx) {
-    constexpr int W = D * (D + 1) / 2;
+  // sum (J dx + r)^T L (J dx + r) over the accepted set; a fixed vertex's
+  // term stays the r^T L r inside chi2Backup.
+  template <typename Kind>
+  T priorKindRho(PriorSet& s, const std::vector<uint8_t>& fixed, const T* dx) {
+    const PriorView<T> p = s.view(true);
     T sum = T(0);
 #pragma omp parallel for num_threads(nt_) schedule(static) \
-    reduction(+ : sum) if (s.m > 4096)
-    for (int64_t k = 0; k < s.m; ++k) {
-      const int v = s.idx[k];
-      T a[D];
-      for (int i = 0; i < D; ++i)
-        a[i] = s.rBak[(size_t)k * D + i] +
-               (fixed[v] ? T(0) : dx[(size_t)v * D + i]);
-      sum += symQuad<T, D>(&s.info[(size_t)k * W], a);
-    }
+    reduction(+ : sum) if (p.m > 4096)
+    for (int64_t k = 0; k < p.m; ++k)
+      sum += priorModel<Kind>(p, k, fixed[p.idx[k]] != 0, dx);
     return sum;
   }
 
   T priorRho() {
-    T cam = paramPriorRho<CD>(camPr_, camFixed_, deltaX_.data());
-    const PriorSet& s = ctrPr_;
-    for (int64_t k = 0; k < s.m; ++k) {
-      const int c = s.idx[k];
-      const T* J = &s.JBak[18 * k];
-      T a[3];
-      for (int b = 0; b < 3; ++b) {
-        a[b] = s.rBak[3 * k + b];
-        if (!camFixed_[c])
-          for (int i = 0; i < 6; ++i)
-            a[b] += J[6 * b + i] * deltaX_[(size_t)c * CD + i];
-      }
-      cam += symQuad<T, 3>(&s.info[6 * k], a);
-    }
+    const T* dxp = deltaX_.data() + (size_t)ncam_ * CD;
+    T cam = priorKindRho<ParamKind<CD>>(camPr_, camFixed_, deltaX_.data());
+    if constexpr (CD >= 6)
+      cam += priorKindRho<CentreKind<CD>>(ctrPr_, camFixed_, deltaX_.data());
     if (rank_ != 0) cam = T(0);
-    return cam + paramPriorRho<PD>(ptPr_, ptFixed_,
-                                   deltaX_.data() + (size_t)ncam_ * CD);
+    return cam + priorKindRho<ParamKind<PD>>(ptPr_, ptFixed_, dxp);
   }
 
   double forwardCustom() {

@@ -43,6 +43,20 @@ inline int gridFor(int64_t n) {
 // ---------------------------------------------------------------------------
 // Reductions
 // ---------------------------------------------------------------------------
+// Tail of the kernels that sum one double per thread into a scalar: block
+// tree, then one atomicAdd per block.  Every thread of a kBlk-wide block must
+// call it.
+__device__ inline void blockSumAtomicAdd(double local, double* acc) {
+  __shared__ double sm[kBlk];
+  sm[threadIdx.x] = local;
+  __syncthreads();
+  for (int s = kBlk / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicAdd(acc, sm[0]);
+}
+
 enum class ROp { Dot, SumSq, AbsMax };
 
 template <typename T, ROp OP>

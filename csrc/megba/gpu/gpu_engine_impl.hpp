@@ -691,45 +691,31 @@ class GpuEngine final : public Engine<T> {
 
  private:
   // ---- unary priors (kernels_prior.hpp) -----------------------------------
-  // One kind's local entries, component-major; r and the centre kind's J are
-  // double-buffered on cur_ exactly like the edge r/J.
+  // One kind's local entries in the layout of prior.hpp; r and the centre
+  // kind's J are double-buffered on cur_ exactly like the edge r/J.
   struct DevPrior {
     int64_t m = 0;
     int* idx{};
-    T *mean{}, *info{};  // [D][m], [D(D+1)/2][m] (identity if unset)
-    T* r[2]{};           // [D][m]
-    T* J[2]{};           // centre kind only: [18][m]
+    T *mean{}, *info{};  // identity information if the list has none
+    T* r[2]{};
+    T* J[2]{};           // centre kind only
+    PriorView<T> view(int b) const { return {m, idx, mean, info, r[b], J[b]}; }
   };
 
   // Keep the entries whose vertex lies in [lo, hi) and upload them.
   template <int D>
   void initPrior(DevPrior& s, const PriorList& l, int lo, int hi, int jw) {
-    constexpr int W = D * (D + 1) / 2;
-    std::vector<size_t> keep;
-    for (size_t k = 0; k < l.idx.size(); ++k)
-      if (l.idx[k] >= lo && l.idx[k] < hi) keep.push_back(k);
-    const int64_t m = (int64_t)keep.size();
+    const PackedPrior h = packPriorList<D>(l, lo, hi);
+    const int64_t m = h.m;
     if (m == 0) return;
-    std::vector<int> idx(m);
-    std::vector<double> mean((size_t)m * D), info((size_t)m * W);
-    for (int64_t q = 0; q < m; ++q) {
-      const size_t k = keep[q];
-      idx[q] = l.idx[k];
-      for (int i = 0; i < D; ++i) mean[(size_t)i * m + q] = l.mean[k * D + i];
-      for (int i = 0; i < D; ++i)
-        for (int j = i; j < D; ++j)
-          info[(size_t)packedIdx<D>(i, j) * m + q] =
-              l.info.empty() ? (i == j ? 1.0 : 0.0)
-                             : l.info[k * W + packedIdx<D>(i, j)];
-    }
     s.m = m;
     s.idx = dalloc<int>(m);
-    HIP_CHECK(hipMemcpy(s.idx, idx.data(), m * sizeof(int),
+    HIP_CHECK(hipMemcpy(s.idx, h.idx.data(), m * sizeof(int),
                         hipMemcpyHostToDevice));
-    s.mean = dalloc<T>(m * D);
-    s.info = dalloc<T>(m * W);
-    upCast(s.mean, mean.data(), m * D);
-    upCast(s.info, info.data(), m * W);
+    s.mean = dalloc<T>(h.mean.size());
+    s.info = dalloc<T>(h.info.size());
+    upCast(s.mean, h.mean.data(), h.mean.size());
+    upCast(s.info, h.info.data(), h.info.size());
     for (int b = 0; b < 2; ++b) {
       s.r[b] = dalloc<T>(m * D);
       HIP_CHECK(hipMemsetAsync(s.r[b], 0, m * D * sizeof(T), stream_));
@@ -750,74 +736,65 @@ class GpuEngine final : public Engine<T> {
     return g < 1024 ? g : 1024;
   }
 
-  // The camera kinds are replicated: rank 0 alone counts their scalars.
-  double* camPriorAcc() { return rank_ == 0 ? scalarPtr() : nullptr; }
+  // What differs between the kinds at a launch: the vertex arrays the kind
+  // lives on and where its scalars are counted.
+  struct PriorSite {
+    const T *x, *dx;
+    T *H, *g;
+    const unsigned char* fixed;
+    double* acc;
+  };
+
+  // f(kind tag, per-row assembly tag, entries, site) for every non-empty
+  // kind: camera parameters, centre, point.  The camera kinds are
+  // replicated, so rank 0 alone counts their scalars; their assembly runs
+  // one thread per block row, the point kind's one thread per prior.
+  template <typename F>
+  void forEachPrior(F&& f) {
+    const PriorSite cam{dParams_, dDeltaX_, dHpp_, dG_, dCamFixed_,
+                        rank_ == 0 ? scalarPtr() : nullptr};
+    const PriorSite pt{dParams_ + nc_, dDeltaX_ + nc_, dHll_, dG_ + nc_,
+                       dPtFixed_, scalarPtr()};
+    if (camPr_.m > 0) f(ParamKind<CD>{}, std::true_type{}, camPr_, cam);
+    if constexpr (CD >= 6) {
+      if (ctrPr_.m > 0) f(CentreKind<CD>{}, std::true_type{}, ctrPr_, cam);
+    }
+    if (ptPr_.m > 0) f(ParamKind<PD>{}, std::false_type{}, ptPr_, pt);
+  }
 
   // r (and the centre J) at the current parameters into the current set;
   // adds this rank's share of sum r^T L r to the scalar accumulator.
   void priorForward() {
-    if (camPr_.m > 0)
-      hipLaunchKernelGGL((kPriorParamForward<T, CD>), dim3(priorRedGrid(camPr_.m)),
-                         dim3(kBlk), 0, stream_, camPr_.m, camPr_.idx,
-                         dParams_, camPr_.mean, camPr_.info, camPr_.r[cur_],
-                         camPriorAcc());
-    if constexpr (CD >= 6) {
-      if (ctrPr_.m > 0)
-        hipLaunchKernelGGL((kPriorCentreForward<T, CD>),
-                           dim3(priorRedGrid(ctrPr_.m)), dim3(kBlk), 0, stream_,
-                           ctrPr_.m, ctrPr_.idx, dParams_, ctrPr_.mean,
-                           ctrPr_.info, ctrPr_.r[cur_], ctrPr_.J[cur_],
-                           camPriorAcc());
-    }
-    if (ptPr_.m > 0)
-      hipLaunchKernelGGL((kPriorParamForward<T, PD>), dim3(priorRedGrid(ptPr_.m)),
-                         dim3(kBlk), 0, stream_, ptPr_.m, ptPr_.idx,
-                         dParams_ + nc_, ptPr_.mean, ptPr_.info, ptPr_.r[cur_],
-                         scalarPtr());
+    forEachPrior([&](auto kind, auto, const DevPrior& s, const PriorSite& at) {
+      const PriorView<T> p = s.view(cur_);
+      hipLaunchKernelGGL((kPriorForward<T, decltype(kind)>),
+                         dim3(priorRedGrid(p.m)), dim3(kBlk), 0, stream_, p.m,
+                         p.idx, p.mean, p.info, p.r, p.J, at.x, at.acc);
+    });
   }
 
   // J^T L J and -J^T L r of the accepted set onto the vertices' own blocks.
   void priorAssemble() {
-    const int bak = cur_ ^ 1;
-    if (camPr_.m > 0)
-      hipLaunchKernelGGL((kPriorParamAssemble<T, CD, true>),
-                         dim3(gridFor(camPr_.m * CD)), dim3(kBlk), 0, stream_,
-                         camPr_.m, camPr_.idx, camPr_.info, camPr_.r[bak],
-                         dCamFixed_, dHpp_, dG_);
-    if constexpr (CD >= 6) {
-      if (ctrPr_.m > 0)
-        hipLaunchKernelGGL((kPriorCentreAssemble<T, CD>),
-                           dim3(gridFor(ctrPr_.m * 6)), dim3(kBlk), 0, stream_,
-                           ctrPr_.m, ctrPr_.idx, ctrPr_.info, ctrPr_.r[bak],
-                           ctrPr_.J[bak], dCamFixed_, dHpp_, dG_);
-    }
-    if (ptPr_.m > 0)
-      hipLaunchKernelGGL((kPriorParamAssemble<T, PD, false>),
-                         dim3(gridFor(ptPr_.m)), dim3(kBlk), 0, stream_,
-                         ptPr_.m, ptPr_.idx, ptPr_.info, ptPr_.r[bak],
-                         dPtFixed_, dHll_, dG_ + nc_);
+    forEachPrior([&](auto kind, auto perRow, const DevPrior& s,
+                     const PriorSite& at) {
+      using Kind = decltype(kind);
+      constexpr bool PER_ROW = decltype(perRow)::value;
+      const PriorView<T> p = s.view(cur_ ^ 1);
+      hipLaunchKernelGGL((kPriorAssemble<T, Kind, PER_ROW>),
+                         dim3(gridFor(PER_ROW ? p.m * Kind::ROWS : p.m)),
+                         dim3(kBlk), 0, stream_, p.m, p.idx, p.info, p.r, p.J,
+                         at.fixed, at.H, at.g);
+    });
   }
 
   // The priors' share of the gain-ratio model, from the accepted set.
   void priorRho() {
-    const int bak = cur_ ^ 1;
-    if (camPr_.m > 0)
-      hipLaunchKernelGGL((kPriorParamRho<T, CD>), dim3(priorRedGrid(camPr_.m)),
-                         dim3(kBlk), 0, stream_, camPr_.m, camPr_.idx,
-                         camPr_.info, camPr_.r[bak], dCamFixed_, dDeltaX_,
-                         camPriorAcc());
-    if constexpr (CD >= 6) {
-      if (ctrPr_.m > 0)
-        hipLaunchKernelGGL((kPriorCentreRho<T, CD>), dim3(priorRedGrid(ctrPr_.m)),
-                           dim3(kBlk), 0, stream_, ctrPr_.m, ctrPr_.idx,
-                           ctrPr_.info, ctrPr_.r[bak], ctrPr_.J[bak],
-                           dCamFixed_, dDeltaX_, camPriorAcc());
-    }
-    if (ptPr_.m > 0)
-      hipLaunchKernelGGL((kPriorParamRho<T, PD>), dim3(priorRedGrid(ptPr_.m)),
-                         dim3(kBlk), 0, stream_, ptPr_.m, ptPr_.idx,
-                         ptPr_.info, ptPr_.r[bak], dPtFixed_, dDeltaX_ + nc_,
-                         scalarPtr());
+    forEachPrior([&](auto kind, auto, const DevPrior& s, const PriorSite& at) {
+      const PriorView<T> p = s.view(cur_ ^ 1);
+      hipLaunchKernelGGL((kPriorRho<T, decltype(kind)>),
+                         dim3(priorRedGrid(p.m)), dim3(kBlk), 0, stream_, p.m,
+                         p.idx, p.info, p.r, p.J, at.fixed, at.dx, at.acc);
+    });
   }
 
   bool weighted() const { return hasInfo_ || lossKind_ != 0; }

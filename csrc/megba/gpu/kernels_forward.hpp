@@ -26,7 +26,6 @@ __global__ __launch_bounds__(256, 2) void kForward(
   using J3 = Jet<T, 3>;
   constexpr int GW = CD + PD;
   constexpr int LANES = (GW + 2) / 3;
-  __shared__ double sm[kBlk];
   double chi2 = 0.0;
   const T* ptsBase = params + (int64_t)ncam * CD;
   const int64_t nWork = nL * LANES;
@@ -66,13 +65,7 @@ __global__ __launch_bounds__(256, 2) void kForward(
       chi2 += (double)lossRho(lossKind, lossD2, (T)ss);
     }
   }
-  sm[threadIdx.x] = chi2;
-  __syncthreads();
-  for (int s = kBlk / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(chi2Acc, sm[0]);
+  blockSumAtomicAdd(chi2, chi2Acc);
 }
 
 // Value-share forward experiment (env MEGBA_FWD_VS=1,
@@ -92,7 +85,6 @@ __global__ __launch_bounds__(256, 2) void kForwardVS(
     T* __restrict__ Jc, T* __restrict__ Jp, double* chi2Acc, int lossKind,
     T lossD2) {
   using J3 = Jet<T, 3>;
-  __shared__ double sm[kBlk];
   double chi2 = 0.0;
   const T* ptsBase = params + (int64_t)ncam * 9;
   const int64_t nWork = nL * 4;
@@ -191,13 +183,7 @@ __global__ __launch_bounds__(256, 2) void kForwardVS(
       chi2 += (double)lossRho(lossKind, lossD2,
                               res[0].v * res[0].v + res[1].v * res[1].v);
   }
-  sm[threadIdx.x] = chi2;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(chi2Acc, sm[0]);
+  blockSumAtomicAdd(chi2, chi2Acc);
 }
 
 // Analytical-derivative forward: one thread per edge, closed-form residual +
@@ -213,7 +199,6 @@ __global__ void kForwardAnalytical(int64_t nL, const int* __restrict__ camOf,
                                    T* __restrict__ rOut, T* __restrict__ Jc,
                                    T* __restrict__ Jp, double* chi2Acc,
                                    int lossKind, T lossD2) {
-  __shared__ double sm[kBlk];
   double chi2 = 0.0;
   const T* ptsBase = params + (int64_t)ncam * 9;
   for (int64_t e = blockIdx.x * (int64_t)kBlk + threadIdx.x; e < nL;
@@ -235,20 +220,13 @@ __global__ void kForwardAnalytical(int64_t nL, const int* __restrict__ camOf,
         Jp[((int64_t)(col * 2 + row)) * nL + e] = pfix ? T(0) : jp[row][col];
     }
   }
-  sm[threadIdx.x] = chi2;
-  __syncthreads();
-  for (int s = kBlk / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(chi2Acc, sm[0]);
+  blockSumAtomicAdd(chi2, chi2Acc);
 }
 
 // chi2 with a robust loss, from the residual buffers (custom-edge path).
 template <typename T, int RD>
 __global__ void kChi2Loss(int64_t nL, const T* __restrict__ r, int lossKind,
                           T lossD2, double* acc) {
-  __shared__ double sm[kBlk];
   double local = 0.0;
   for (int64_t e = blockIdx.x * (int64_t)kBlk + threadIdx.x; e < nL;
        e += (int64_t)gridDim.x * kBlk) {
@@ -259,13 +237,7 @@ __global__ void kChi2Loss(int64_t nL, const T* __restrict__ r, int lossKind,
     }
     local += (double)lossRho(lossKind, lossD2, ss);
   }
-  sm[threadIdx.x] = local;
-  __syncthreads();
-  for (int s = kBlk / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(acc, sm[0]);
+  blockSumAtomicAdd(local, acc);
 }
 
 // Custom-edge support: gather parameter leaves, repack residual JetVectors.
