@@ -78,9 +78,36 @@ __device__ __forceinline__ void tailBroadcast(bool tail, int lane,
   for (int k = 0; k < PD; ++k) wv[k] = __shfl(wv[k], tl, 64);
 }
 
+// Wave sum by the __shfl_down ladder (32, 16, ... 1): lane 0 ends up with the
+// sum over the 64 lanes, of every element of a or of one value.
+template <typename T, int N>
+__device__ __forceinline__ void waveSumDown(T (&a)[N]) {
+  for (int off = 32; off > 0; off >>= 1)
+    for (int i = 0; i < N; ++i) a[i] += __shfl_down(a[i], off, 64);
+}
+template <typename T>
+__device__ __forceinline__ T waveSumDown(T v) {
+  T a[1] = {v};
+  waveSumDown(a);
+  return a[0];
+}
+
 // ---------------------------------------------------------------------------
+// Block-diagonal products
+// ---------------------------------------------------------------------------
+// Row `row` of block b of a block-diagonal matrix (D x D blocks, row-major)
+// times that block's vector x (D values, in global memory or LDS): j
+// ascending from T(0).
+template <typename T, int D>
+__device__ __forceinline__ T blockRowDot(const T* __restrict__ A, int64_t b,
+                                         int row, const T* x) {
+  const T* r = A + b * D * D + (int64_t)row * D;
+  T s = T(0);
+  for (int j = 0; j < D; ++j) s += r[j] * x[j];
+  return s;
+}
+
 // Cinv block apply  w = HllInv[pt] * t  (PD x PD, row-major)
-// ---------------------------------------------------------------------------
 template <typename T, int PD, typename In, typename Out>
 __device__ __forceinline__ void cinvApply(const T* inv, const In& t, Out& w) {
   for (int i = 0; i < PD; ++i) {

@@ -43,25 +43,68 @@ inline int gridFor(int64_t n) {
 // ---------------------------------------------------------------------------
 // Reductions
 // ---------------------------------------------------------------------------
-// Tail of the kernels that sum one double per thread into a scalar: block
-// tree, then one atomicAdd per block.  Every thread of a kBlk-wide block must
-// call it.
-__device__ inline void blockSumAtomicAdd(double local, double* acc) {
+enum class ROp { Dot, SumSq, AbsMax };
+
+// Block tree over one double per thread: max for AbsMax, sum otherwise.
+// Every thread of a kBlk-wide block must call it and every thread gets the
+// block's result.  The tree halves from kBlk / 2, which fixes the summation
+// order.  It ends behind a barrier, so it can be called again right away.
+template <ROp OP>
+__device__ inline double blockReduce(double v) {
   __shared__ double sm[kBlk];
-  sm[threadIdx.x] = local;
+  sm[threadIdx.x] = v;
   __syncthreads();
   for (int s = kBlk / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+    if (threadIdx.x < s) {
+      if (OP == ROp::AbsMax)
+        sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + s]);
+      else
+        sm[threadIdx.x] += sm[threadIdx.x + s];
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) atomicAdd(acc, sm[0]);
+  const double total = sm[0];
+  __syncthreads();
+  return total;
+}
+__device__ inline double blockSum(double v) {
+  return blockReduce<ROp::Dot>(v);
 }
 
-enum class ROp { Dot, SumSq, AbsMax };
+// Reduce a partial array (one value per block of an earlier kernel): thread t
+// takes part[t], part[t + kBlk], ... in that order, then the block tree.
+template <ROp OP>
+__device__ inline double partialsReduce(const double* __restrict__ part,
+                                        int nb) {
+  double v = 0.0;
+  for (int i = threadIdx.x; i < nb; i += kBlk) {
+    if (OP == ROp::AbsMax)
+      v = fmax(v, part[i]);
+    else
+      v += part[i];
+  }
+  return blockReduce<OP>(v);
+}
+__device__ inline double partialsSum(const double* __restrict__ part,
+                                     int nb) {
+  return partialsReduce<ROp::Dot>(part, nb);
+}
+
+// Tail of the kernels that sum one double per thread into a scalar: block
+// tree, then one atomicAdd per block.
+__device__ inline void blockSumAtomicAdd(double local, double* acc) {
+  const double total = blockSum(local);
+  if (threadIdx.x == 0) atomicAdd(acc, total);
+}
+
+// num / den, 0 where den is 0: the PCG scalars beta = rho / rhoPrev and
+// alpha = rho / p.q.
+__device__ inline double safeRatio(double num, double den) {
+  return den != 0.0 ? num / den : 0.0;
+}
 
 template <typename T, ROp OP>
 __global__ void kRedPartial(const T* a, const T* b, int64_t n, double* part) {
-  __shared__ double sm[kBlk];
   double v = 0.0;
   for (int64_t i = blockIdx.x * (int64_t)kBlk + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kBlk) {
@@ -73,42 +116,14 @@ __global__ void kRedPartial(const T* a, const T* b, int64_t n, double* part) {
     else
       v = fmax(v, fabs(x));
   }
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kBlk / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      if (OP == ROp::AbsMax)
-        sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + s]);
-      else
-        sm[threadIdx.x] += sm[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
+  const double total = blockReduce<OP>(v);
+  if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
 template <ROp OP>
 __global__ void kRedFinal(const double* part, int nb, double* out) {
-  __shared__ double sm[kBlk];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < nb; i += kBlk) {
-    if (OP == ROp::AbsMax)
-      v = fmax(v, part[i]);
-    else
-      v += part[i];
-  }
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kBlk / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) {
-      if (OP == ROp::AbsMax)
-        sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + s]);
-      else
-        sm[threadIdx.x] += sm[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = sm[0];
+  const double total = partialsReduce<OP>(part, nb);
+  if (threadIdx.x == 0) *out = total;
 }
 
 }  // namespace

@@ -1,10 +1,12 @@
 // PCG vector kernels (seven-kernel and rotated body), back-substitution and
-// the rho denominator.
+// the rho denominator.  Their reductions (blockSum, partialsSum,
+// blockSumAtomicAdd, safeRatio) are in gpu_common.hpp, the block-row product
+// and the wave sum in edge_ops.hpp, the LDS row reduce in kernels_product.hpp.
 #pragma once
 
 #include "edge_ops.hpp"
 #include "gpu_common.hpp"
-#include "kernels_product.hpp"  // kLdsRedWaves
+#include "kernels_product.hpp"  // ldsRowsColumnSum
 
 namespace megba {
 namespace {
@@ -15,26 +17,16 @@ template <typename T, int CD>
 __global__ void kPrecondRho(int nBlk, const T* __restrict__ Binv,
                             const T* __restrict__ r, T* __restrict__ z,
                             double* part) {
-  __shared__ double sm[kBlk];
   double local = 0.0;
   for (int64_t idx = blockIdx.x * (int64_t)kBlk + threadIdx.x;
        idx < (int64_t)nBlk * CD; idx += (int64_t)gridDim.x * kBlk) {
     const int64_t b = idx / CD;
-    const int rr = (int)(idx % CD);
-    const T* row = Binv + b * CD * CD + (int64_t)rr * CD;
-    const T* xb = r + b * CD;
-    T sv = T(0);
-    for (int j = 0; j < CD; ++j) sv += row[j] * xb[j];
+    const T sv = blockRowDot<T, CD>(Binv, b, (int)(idx % CD), r + b * CD);
     z[idx] = sv;
     local += (double)sv * (double)r[idx];
   }
-  sm[threadIdx.x] = local;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
+  const double total = blockSum(local);
+  if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
 // B-apply (y = A x - y, the Schur S-apply tail) fused with the per-block
@@ -44,27 +36,16 @@ template <typename T, int CD>
 __global__ void kBApplyDot(int nBlk, const T* __restrict__ A,
                            const T* __restrict__ x, T* __restrict__ y,
                            double* part) {
-  __shared__ double sm[kBlk];
   double local = 0.0;
   for (int64_t idx = blockIdx.x * (int64_t)kBlk + threadIdx.x;
        idx < (int64_t)nBlk * CD; idx += (int64_t)gridDim.x * kBlk) {
     const int64_t b = idx / CD;
-    const int rrow = (int)(idx % CD);
-    const T* row = A + b * CD * CD + (int64_t)rrow * CD;
-    const T* xb = x + b * CD;
-    T s = T(0);
-    for (int j = 0; j < CD; ++j) s += row[j] * xb[j];
-    const T q = s - y[idx];
+    const T q = blockRowDot<T, CD>(A, b, (int)(idx % CD), x + b * CD) - y[idx];
     y[idx] = q;
     local += (double)x[idx] * (double)q;
   }
-  sm[threadIdx.x] = local;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
+  const double total = blockSum(local);
+  if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
 // ---------------------------------------------------------------------------
@@ -96,19 +77,9 @@ __global__ void kXpbySBeta(int64_t n, const T* __restrict__ z,
                            const double* __restrict__ part, int nb,
                            const double* __restrict__ rhoPrev,
                            double* __restrict__ rhoOut, T* __restrict__ p) {
-  __shared__ double sm[kBlk];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < nb; i += kBlk) v += part[i];
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  const double rho = sm[0];
+  const double rho = partialsSum(part, nb);
   if (blockIdx.x == 0 && threadIdx.x == 0) *rhoOut = rho;
-  const double rp = *rhoPrev;
-  const T beta = (T)(rp != 0.0 ? rho / rp : 0.0);
+  const T beta = (T)safeRatio(rho, *rhoPrev);
   for (int64_t i = blockIdx.x * (int64_t)kBlk + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kBlk)
     p[i] = z[i] + beta * p[i];
@@ -126,25 +97,10 @@ __global__ void kUpdateXRAlpha(int64_t n, const double* __restrict__ partR,
                                const T* __restrict__ q, T* __restrict__ x,
                                T* __restrict__ xBak,
                                T* __restrict__ xBakPrev, T* __restrict__ r) {
-  __shared__ double smR[kBlk];
-  __shared__ double smQ[kBlk];
-  double vR = 0.0, vQ = 0.0;
-  for (int i = threadIdx.x; i < nbR; i += kBlk) vR += partR[i];
-  for (int i = threadIdx.x; i < nbQ; i += kBlk) vQ += partQ[i];
-  smR[threadIdx.x] = vR;
-  smQ[threadIdx.x] = vQ;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) {
-      smR[threadIdx.x] += smR[threadIdx.x + st];
-      smQ[threadIdx.x] += smQ[threadIdx.x + st];
-    }
-    __syncthreads();
-  }
-  const double rho = smR[0];
-  const double pq = smQ[0];
+  const double rho = partialsSum(partR, nbR);
+  const double pq = partialsSum(partQ, nbQ);
   if (blockIdx.x == 0 && threadIdx.x == 0) *rhoPrevOut = rho;
-  const T a = (T)(pq != 0.0 ? rho / pq : 0.0);
+  const T a = (T)safeRatio(rho, pq);
   for (int64_t i = blockIdx.x * (int64_t)kBlk + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kBlk) {
     xBakPrev[i] = xBak[i];
@@ -164,6 +120,9 @@ __global__ void kUpdateXRAlpha(int64_t n, const double* __restrict__ partR,
 //   kBetaPPad          = kXpbySBeta + kPadX
 //   kLdsReduceBApplyDot = kLdsRowsReduce + kBApplyDot
 //   kUpdateXRPrecond   = kUpdateXRAlpha + kPrecondRho
+// Each merged kernel calls the device functions its two halves call
+// (partialsSum and safeRatio, ldsRowsColumnSum, blockRowDot, blockSum), so
+// the sums of the two bodies are the same code.
 
 // beta + p-update (as kXpbySBeta) that also writes the XP-padded copy of the
 // new p in kPadX's layout and to kPadX's (dst, stride, off), zero pad lanes
@@ -176,19 +135,9 @@ __global__ void kBetaPPad(int ncam, const T* __restrict__ z,
                           T* __restrict__ dst, int stride, int off) {
   constexpr int VEC = PackVec<T>::VEC;
   constexpr int XP = (CD + VEC - 1) / VEC * VEC;
-  __shared__ double sm[kBlk];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < nb; i += kBlk) v += part[i];
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  const double rho = sm[0];
+  const double rho = partialsSum(part, nb);
   if (blockIdx.x == 0 && threadIdx.x == 0) *rhoOut = rho;
-  const double rp = *rhoPrev;
-  const T beta = (T)(rp != 0.0 ? rho / rp : 0.0);
+  const T beta = (T)safeRatio(rho, *rhoPrev);
   for (int64_t idx = blockIdx.x * (int64_t)kBlk + threadIdx.x;
        idx < (int64_t)ncam * XP; idx += (int64_t)gridDim.x * kBlk) {
     const int64_t c = idx / XP;
@@ -212,36 +161,18 @@ template <typename T, int CD>
 __global__ __launch_bounds__(64 * kLdsRedWaves) void kLdsReduceBApplyDot(
     int G, int nc, const T* __restrict__ rows, const T* __restrict__ A,
     const T* __restrict__ p, T* __restrict__ out, double* __restrict__ part) {
-  __shared__ T sm[kLdsRedWaves][64];
-  const int lane = threadIdx.x & 63;
-  const int col = blockIdx.x * 64 + lane;
-  const int q = (int)threadIdx.x >> 6;
-  const int g0 = (int)((int64_t)G * q / kLdsRedWaves);
-  const int g1 = (int)((int64_t)G * (q + 1) / kLdsRedWaves);
-  T s = T(0);
-  if (col < nc) {
-#pragma unroll 8
-    for (int g = g0; g < g1; ++g) s += rows[(int64_t)g * nc + col];
-  }
-  sm[q][lane] = s;
-  __syncthreads();
-  if (q != 0) return;
+  const int col = blockIdx.x * 64 + (threadIdx.x & 63);
+  const T v = ldsRowsColumnSum<T>(G, nc, rows, col);
+  if (threadIdx.x >= 64) return;
   double local = 0.0;
   if (col < nc) {
-    T v = sm[0][lane];
-    for (int k = 1; k < kLdsRedWaves; ++k) v += sm[k][lane];
     const int b = col / CD;
-    const int rrow = col % CD;
-    const T* row = A + (int64_t)b * CD * CD + rrow * CD;
-    const T* xb = p + (int64_t)b * CD;
-    T hp = T(0);
-    for (int j = 0; j < CD; ++j) hp += row[j] * xb[j];
-    const T qv = hp - v;
+    const T qv = blockRowDot<T, CD>(A, b, col % CD, p + (int64_t)b * CD) - v;
     out[col] = qv;
     local = (double)p[col] * (double)qv;
   }
-  for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
-  if (lane == 0) part[blockIdx.x] = local;
+  local = waveSumDown(local);
+  if (threadIdx.x == 0) part[blockIdx.x] = local;
 }
 
 // alpha + x/r update (as kUpdateXRAlpha, backup rotation included) followed
@@ -260,21 +191,11 @@ __global__ __launch_bounds__(kBlk) void kUpdateXRPrecond(
     T* __restrict__ xBakPrev, T* __restrict__ r, const T* __restrict__ Binv,
     T* __restrict__ z, double* __restrict__ part) {
   constexpr int CPB = kBlk / CD;  // cameras per block
-  __shared__ double sm[kBlk];
   __shared__ T rNew[CPB * CD];
-  double vQ = 0.0;
-  for (int i = threadIdx.x; i < nbQ; i += kBlk) vQ += partQ[i];
-  sm[threadIdx.x] = vQ;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  const double pq = sm[0];
+  const double pq = partialsSum(partQ, nbQ);
   const double rho = *rhoIn;
-  __syncthreads();  // sm is reused for the rho partial below
   if (blockIdx.x == 0 && threadIdx.x == 0) *rhoPrevOut = rho;
-  const T a = (T)(pq != 0.0 ? rho / pq : 0.0);
+  const T a = (T)safeRatio(rho, pq);
   const int t = (int)threadIdx.x;
   const int cl = t / CD;  // camera within the block
   const int64_t cam = (int64_t)blockIdx.x * CPB + cl;
@@ -290,23 +211,15 @@ __global__ __launch_bounds__(kBlk) void kUpdateXRPrecond(
     r[i] = rn;
     rNew[t] = rn;
   }
-  __syncthreads();
+  __syncthreads();  // rNew: a camera's rows are other threads' values
   double local = 0.0;
   if (live) {
-    const T* row = Binv + cam * CD * CD + (int64_t)(t - cl * CD) * CD;
-    const T* xb = rNew + cl * CD;
-    T sv = T(0);
-    for (int j = 0; j < CD; ++j) sv += row[j] * xb[j];
+    const T sv = blockRowDot<T, CD>(Binv, cam, t - cl * CD, rNew + cl * CD);
     z[i] = sv;
     local = (double)sv * (double)rn;
   }
-  sm[threadIdx.x] = local;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
+  const double total = blockSum(local);
+  if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
 
 // r = v - q
@@ -343,14 +256,10 @@ __global__ void kBackSub(int npt, const T* __restrict__ HllInv,
                          T* __restrict__ dxp) {
   for (int64_t p = blockIdx.x * (int64_t)kBlk + threadIdx.x; p < npt;
        p += (int64_t)gridDim.x * kBlk) {
-    const T* inv = HllInv + p * PD * PD;
     T rhs[PD];
     for (int i = 0; i < PD; ++i) rhs[i] = gp[PD * p + i] - temp[PD * p + i];
-    for (int i = 0; i < PD; ++i) {
-      T v = T(0);
-      for (int j = 0; j < PD; ++j) v += inv[i * PD + j] * rhs[j];
-      dxp[PD * p + i] = v;
-    }
+    T* out = dxp + PD * p;
+    cinvApply<T, PD>(HllInv + p * PD * PD, rhs, out);
   }
 }
 
@@ -363,7 +272,6 @@ __global__ void kRhoDenom(int64_t nL, const int* __restrict__ camOf,
                           const T* __restrict__ Jc, const T* __restrict__ Jp,
                           const T* __restrict__ dxc, const T* __restrict__ dxp,
                           double* acc, int lossKind, T lossD2) {
-  __shared__ double sm[kBlk];
   double local = 0.0;
   for (int64_t e = blockIdx.x * (int64_t)kBlk + threadIdx.x; e < nL;
        e += (int64_t)gridDim.x * kBlk) {
@@ -380,13 +288,7 @@ __global__ void kRhoDenom(int64_t nL, const int* __restrict__ camOf,
     }
     local += (double)lossRho(lossKind, lossD2, ss);
   }
-  sm[threadIdx.x] = local;
-  __syncthreads();
-  for (int s = kBlk / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(acc, sm[0]);
+  blockSumAtomicAdd(local, acc);
 }
 
 // Packed-J rho denominator (implicit mode): the accepted [Jc, Jp] vector
@@ -400,7 +302,6 @@ __global__ void kRhoDenomPk(int64_t nL, const int* __restrict__ camOf,
                             const T* __restrict__ dxcPad,
                             const T* __restrict__ dxp, double* acc,
                             int lossKind, T lossD2) {
-  __shared__ double sm[kBlk];
   double local = 0.0;
   for (int64_t e = blockIdx.x * (int64_t)kBlk + threadIdx.x; e < nL;
        e += (int64_t)gridDim.x * kBlk) {
@@ -422,13 +323,7 @@ __global__ void kRhoDenomPk(int64_t nL, const int* __restrict__ camOf,
     }
     local += (double)lossRho(lossKind, lossD2, ss);
   }
-  sm[threadIdx.x] = local;
-  __syncthreads();
-  for (int st = kBlk / 2; st > 0; st >>= 1) {
-    if (threadIdx.x < st) sm[threadIdx.x] += sm[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(acc, sm[0]);
+  blockSumAtomicAdd(local, acc);
 }
 
 }  // namespace

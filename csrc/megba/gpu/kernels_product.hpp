@@ -137,6 +137,49 @@ __global__ void kSpmvEtxPkAtomic(int64_t nL, const int* __restrict__ camOf,
   }
 }
 
+// ---------------------------------------------------------------------------
+// E w chunk kernels (kSpmvEx, kSpmvExPk): one wave per <=256-row chunk of
+// one camera's cam-sorted rows
+// ---------------------------------------------------------------------------
+// This wave's chunk: its camera and row range [lo, hi); false past the table.
+__device__ __forceinline__ bool exChunk(int nChunks,
+                                        const int* __restrict__ chCam,
+                                        const int* __restrict__ chLo,
+                                        const int* __restrict__ chHi,
+                                        int& cam, int& lo, int& hi) {
+  const int chunk = blockIdx.x;
+  if (chunk >= nChunks) return false;
+  cam = chCam[chunk];
+  lo = chLo[chunk];
+  hi = chHi[chunk];
+  return true;
+}
+
+// w is stored 4-padded (stride 4 elements, 16B/32B aligned) so the
+// per-edge gather is 1 (fp32) or 2 (fp64) vector loads instead of PD
+// scalar loads — the gather is the TA-request hot spot of these kernels.
+template <typename T>
+constexpr int kWPadVecs = (4 * (int)sizeof(T) + 15) / 16;
+template <typename T>
+__device__ __forceinline__ void loadWPadded(
+    const T* __restrict__ w, int pt,
+    typename PackVec<T>::type (&wbuf)[kWPadVecs<T>]) {
+  using TV = typename PackVec<T>::type;
+  const TV* wp4 = (const TV*)(w + (int64_t)pt * 4);
+#pragma unroll
+  for (int l = 0; l < kWPadVecs<T>; ++l) wbuf[l] = wp4[l];
+}
+
+// Lane 0 (which holds the wave sum) adds the chunk's CD values to its camera.
+template <typename T, int CD>
+__device__ __forceinline__ void exFlush(const T (&acc)[CD], int cam,
+                                        T* __restrict__ out) {
+  if (threadIdx.x == 0) {
+    T* oc = out + (int64_t)cam * CD;
+    for (int i = 0; i < CD; ++i) atomicAdd(&oc[i], acc[i]);
+  }
+}
+
 // Packed E w over the cam-sorted [wJc(CR), Jp(PR)] groups.
 template <typename T, int CD, int PD, int RD>
 __global__ __launch_bounds__(64) void kSpmvExPk(
@@ -148,22 +191,14 @@ __global__ __launch_bounds__(64) void kSpmvExPk(
   constexpr int VEC = PackVec<T>::VEC;
   constexpr int CR = CD * RD, PR = PD * RD;
   constexpr int NG = PackedEdge<T, CD, PD, RD, true>::NG;
-  const int chunk = blockIdx.x;
-  if (chunk >= nChunks) return;
-  const int cam = chCam[chunk];
+  int cam, lo, hi;
+  if (!exChunk(nChunks, chCam, chLo, chHi, cam, lo, hi)) return;
   T acc[CD];
   for (int i = 0; i < CD; ++i) acc[i] = T(0);
-  const int lo = chLo[chunk], hi = chHi[chunk];
   const TV* src = (const TV*)JCamPk;
-  // w is stored 4-padded (stride 4 elements, 16B/32B aligned) so the
-  // per-edge gather is 1 (fp32) or 2 (fp64) vector loads instead of PD
-  // scalar loads — the gather is the TA-request hot spot of this kernel.
-  constexpr int WL = (4 * (int)sizeof(T) + 15) / 16;
   for (int j = lo + (int)threadIdx.x; j < hi; j += 64) {
-    const TV* wp4 = (const TV*)(w + (int64_t)ptOfCam[j] * 4);
-    TV wbuf[WL];
-#pragma unroll
-    for (int l = 0; l < WL; ++l) wbuf[l] = wp4[l];
+    TV wbuf[kWPadVecs<T>];
+    loadWPadded<T>(w, ptOfCam[j], wbuf);
     TV buf[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) buf[g] = src[(int64_t)g * nL + j];
@@ -189,12 +224,8 @@ __global__ __launch_bounds__(64) void kSpmvExPk(
       acc[i] += v;
     }
   }
-  for (int off = 32; off > 0; off >>= 1)
-    for (int i = 0; i < CD; ++i) acc[i] += __shfl_down(acc[i], off, 64);
-  if (threadIdx.x == 0) {
-    T* oc = out + (int64_t)cam * CD;
-    for (int i = 0; i < CD; ++i) atomicAdd(&oc[i], acc[i]);
-  }
+  waveSumDown(acc);
+  exFlush<T, CD>(acc, cam, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -244,19 +275,14 @@ __global__ __launch_bounds__(64) void kSpmvEx(
   using TV = typename PackVec<T>::type;
   constexpr int VEC = PackVec<T>::VEC;
   constexpr int NGH = (CD * PD + VEC - 1) / VEC;
-  constexpr int WL = (4 * (int)sizeof(T) + 15) / 16;
-  const int chunk = blockIdx.x;
-  if (chunk >= nChunks) return;
-  const int cam = chCam[chunk];
+  int cam, lo, hi;
+  if (!exChunk(nChunks, chCam, chLo, chHi, cam, lo, hi)) return;
   T acc[CD];
   for (int i = 0; i < CD; ++i) acc[i] = T(0);
-  const int lo = chLo[chunk], hi = chHi[chunk];
   const TV* src = (const TV*)HplCam;
   for (int j = lo + (int)threadIdx.x; j < hi; j += 64) {
-    const TV* wp4 = (const TV*)(w + (int64_t)ptOfCam[j] * 4);
-    TV wbuf[WL];
-#pragma unroll
-    for (int l = 0; l < WL; ++l) wbuf[l] = wp4[l];
+    TV wbuf[kWPadVecs<T>];
+    loadWPadded<T>(w, ptOfCam[j], wbuf);
     TV buf[NGH];
 #pragma unroll
     for (int g = 0; g < NGH; ++g) buf[g] = src[(int64_t)g * nL + j];
@@ -271,12 +297,8 @@ __global__ __launch_bounds__(64) void kSpmvEx(
       acc[i] += v;
     }
   }
-  for (int off = 32; off > 0; off >>= 1)
-    for (int i = 0; i < CD; ++i) acc[i] += __shfl_down(acc[i], off, 64);
-  if (threadIdx.x == 0) {
-    T* oc = out + (int64_t)cam * CD;
-    for (int i = 0; i < CD; ++i) atomicAdd(&oc[i], acc[i]);
-  }
+  waveSumDown(acc);
+  exFlush<T, CD>(acc, cam, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -947,17 +969,18 @@ __global__ __launch_bounds__(kLdsRcMaxThreads) void kSchurFusedLdsRc(
   for (int i = (int)threadIdx.x; i < nc; i += (int)blockDim.x) row[i] = acc[i];
 }
 
-// out[i] = sum over the G workgroup rows, in fixed order (overwrites out).
-// 64 columns per block; each of the block's kLdsRedWaves waves sums a
-// contiguous share of the G rows, and wave 0 combines the shares through
-// LDS in fixed order.
+// Column sum over the G workgroup rows, in fixed order.  64 columns per
+// block of kLdsRedWaves waves; every thread calls it with its column
+// blockIdx.x * 64 + lane.  Each wave sums a contiguous share of the G rows,
+// and wave 0 combines the shares through LDS in fixed order: the sum is
+// returned to wave 0's lanes with col < nc, T(0) to everyone else.
 constexpr int kLdsRedWaves = 16;
 template <typename T>
-__global__ __launch_bounds__(64 * kLdsRedWaves) void kLdsRowsReduce(
-    int G, int nc, const T* __restrict__ rows, T* __restrict__ out) {
+__device__ __forceinline__ T ldsRowsColumnSum(int G, int nc,
+                                              const T* __restrict__ rows,
+                                              int col) {
   __shared__ T sm[kLdsRedWaves][64];
   const int lane = threadIdx.x & 63;
-  const int col = blockIdx.x * 64 + lane;
   const int q = (int)threadIdx.x >> 6;
   const int g0 = (int)((int64_t)G * q / kLdsRedWaves);
   const int g1 = (int)((int64_t)G * (q + 1) / kLdsRedWaves);
@@ -968,11 +991,21 @@ __global__ __launch_bounds__(64 * kLdsRedWaves) void kLdsRowsReduce(
   }
   sm[q][lane] = s;
   __syncthreads();
+  T v = T(0);
   if (q == 0 && col < nc) {
-    T v = sm[0][lane];
+    v = sm[0][lane];
     for (int k = 1; k < kLdsRedWaves; ++k) v += sm[k][lane];
-    out[col] = v;
   }
+  return v;
+}
+
+// out[i] = sum over the G workgroup rows (overwrites out).
+template <typename T>
+__global__ __launch_bounds__(64 * kLdsRedWaves) void kLdsRowsReduce(
+    int G, int nc, const T* __restrict__ rows, T* __restrict__ out) {
+  const int col = blockIdx.x * 64 + (threadIdx.x & 63);
+  const T v = ldsRowsColumnSum<T>(G, nc, rows, col);
+  if (threadIdx.x < 64 && col < nc) out[col] = v;
 }
 
 // Block-diagonal matvec, one thread per output row.
@@ -983,11 +1016,7 @@ __global__ void kBlockDiagMatVec(int nBlk, const T* __restrict__ A,
   for (int64_t idx = blockIdx.x * (int64_t)kBlk + threadIdx.x;
        idx < (int64_t)nBlk * D; idx += (int64_t)gridDim.x * kBlk) {
     const int64_t b = idx / D;
-    const int rrow = (int)(idx % D);
-    const T* row = A + b * D * D + (int64_t)rrow * D;
-    const T* xb = x + b * D;
-    T s = T(0);
-    for (int j = 0; j < D; ++j) s += row[j] * xb[j];
+    const T s = blockRowDot<T, D>(A, b, (int)(idx % D), x + b * D);
     y[idx] = (MODE == 0) ? s : s - y[idx];
   }
 }
