@@ -7,6 +7,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <memory>
 
 #include "megba/bal_functor.hpp"
@@ -19,6 +20,7 @@
 #include "megba/problem.hpp"
 #include "megba/gpu/edge_tables.hpp"  // host-only
 #include "megba/gpu/rc_tile.hpp"      // host-only
+#include "megba/gpu/schur_plan.hpp"   // host-only
 
 #ifdef MEGBA_WITH_GPU
 #include "megba/gpu/gpu_engine.hpp"
@@ -595,6 +597,65 @@ PYBIND11_MODULE(_core, m) {
         return rcStagedLdsBytes(nc, elemBytes, waves);
       },
       py::arg("nc"), py::arg("elem_bytes"), py::arg("waves"));
+
+  // The GPU engine's choice of the Schur product and its PCG plan
+  // (schur_plan.hpp) as pure functions: the knobs are keywords, the probe
+  // launches and timings arguments; nothing reads the environment or a device.
+  py::enum_<SchurPath>(m, "SchurPath")
+      .value("Lds", SchurPath::Lds)
+      .value("LdsRecompute", SchurPath::LdsRecompute)
+      .value("FusedEtx", SchurPath::FusedEtx)
+      .value("Separate", SchurPath::Separate)
+      .value("OnePass", SchurPath::OnePass);
+  m.def("schur_path_name", &schurPathName);
+  // -> (path or None for "time the candidates", probe launches made in
+  // order, whether lds / lds-recompute are candidates afterwards)
+  m.def(
+      "schur_path_untimed",
+      [](long long nL, bool ldsEligible, bool rcEligible, bool ldsLaunches,
+         bool rcLaunches, bool etxFuse, bool noEtxFuse, bool schurLds,
+         bool schurRecompute) {
+        GpuKnobs k;
+        k.etxFuse = etxFuse;
+        k.noEtxFuse = noEtxFuse;
+        k.schurLds = schurLds;
+        k.schurRecompute = schurRecompute;
+        std::vector<SchurPath> probes;
+        const SchurUntimed u = schurPathUntimed(
+            schurCandidates(k, ldsEligible, rcEligible, nL), [&](SchurPath p) {
+              probes.push_back(p);
+              return p == SchurPath::Lds ? ldsLaunches : rcLaunches;
+            });
+        return py::make_tuple(u.path, probes, u.lds, u.rc);
+      },
+      py::arg("n_local_edges"), py::arg("lds_eligible"),
+      py::arg("rc_eligible"), py::arg("lds_launches") = true,
+      py::arg("rc_launches") = true, py::arg("etxfuse") = false,
+      py::arg("no_etxfuse") = false, py::arg("schur_lds") = false,
+      py::arg("schur_recompute") = false);
+  // ms = [fused-etx, separate, lds, lds-recompute]
+  m.def(
+      "schur_path_from_timings",
+      [](std::array<float, 4> ms, bool ldsTimed, bool rcTimed) {
+        return schurPathFromTimings(ms.data(), ldsTimed, rcTimed);
+      },
+      py::arg("ms"), py::arg("lds_timed"), py::arg("rc_timed"));
+  // -> (path, rotatedBody, productReadsPad, mergeReduceBApply)
+  m.def(
+      "pcg_plan",
+      [](SchurPath tuned, bool implicit, int nLongPts, bool allreduceIsNoop,
+         bool fused, bool noPcgFuse) {
+        GpuKnobs k;
+        k.fused = fused;
+        k.noPcgFuse = noPcgFuse;
+        const PcgPlan p =
+            makePcgPlan(tuned, k, implicit, nLongPts, allreduceIsNoop);
+        return py::make_tuple(p.path, p.rotatedBody, p.productReadsPad,
+                              p.mergeReduceBApply);
+      },
+      py::arg("tuned"), py::arg("implicit"), py::arg("n_long_pts"),
+      py::arg("allreduce_is_noop"), py::arg("fused") = false,
+      py::arg("no_pcg_fuse") = false);
 
 #ifdef MEGBA_WITH_GPU
   m.attr("has_gpu_support") = true;

@@ -1,7 +1,6 @@
 // MI355X (gfx950) engine: HIP kernels + host orchestration + RCCL collectives.
 //
-// Kernel / distribution design (MI355X-first redesign, not a port —
-// behavioural anchors cite /root/reference):
+// Kernel / distribution design (MI355X-first redesign, not a port):
 //  * Observations are (point, camera)-sorted and partitioned on POINT
 //    boundaries: each rank owns its points outright, so the whole point side
 //    (Hll, g_p, Cinv, E^T x, back-substitution) is communication-free and
@@ -10,32 +9,11 @@
 //    the point side instead and allreduces 3*npt words (24 MB on Venice)
 //    per iteration (its sites A1/A3-A6) — a ~190x traffic reduction sized
 //    for xGMI's per-link ring bandwidth.
-//  * kForward fuses the ENTIRE vectorised-autodiff forward pass into one
-//    kernel: each observation is handled by 4 consecutive lanes, each lane
-//    carrying a Jet<T,3> slice of the 12-wide dual part, so every
-//    intermediate of the reprojection expression lives in VGPRs.  The
-//    reference launches ~1 CUDA kernel per elementary op and streams
-//    (N+1)*nItem doubles through HBM each time
-//    (src/operator/jet_vector_math_impl.cu).
-//  * Assembly transports the camera-side per-edge data through a cam-sorted
-//    edge-major slab (contiguous ~400 B per edge, ~1 line-fetch per 64 B)
-//    instead of per-element transpose gathers (8x amplification) or
-//    per-element atomics (the all-atomic version measured 40.8 ms on
-//    Venice-5M, profiles/r01_venice_single_gpu.md).  Point-side Hll/g_p
-//    accumulate with a wave-level segmented scan over the point-sorted runs
-//    — atomics only at segment tails.
 //  * Control-flow scalars (rho, p^T q, norms) use fixed-shape two-pass
 //    deterministic reductions so every rank takes identical PCG branches.
-//  * r2 additions: every kernel and the engine are templated over the
-//    block dims (camDim, ptDim, resDim) — instantiation TUs
-//    gpu_dims_*.hip, runtime dispatch in gpu_engine.hip; the per-
-//    iteration product kernels read 16-byte packed vector-group J/Hpl
-//    layouts with 4-padded w and XP-padded x gathers; the camera-chunk
-//    table is point-band-blocked so the gathered w slice stays
-//    L2-resident; the PCG body is hipGraph-captured (incl. the RCCL
-//    allreduce) with device pointer-slot indirection for the double-
-//    buffered J set; fused-vs-separate E^T x + Cinv is auto-tuned per
-//    problem.  Measured history: profiles/r02_gather_bands.md.
+// The fused forward kernel, the slab assembly, the packed layouts, the
+// captured PCG body and the choice of the Schur product: docs/INTERNALS.md
+// sections 4 to 6.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -61,27 +39,9 @@
 #include "kernels_prior.hpp"
 #include "kernels_product.hpp"
 #include "knobs.hpp"
+#include "schur_plan.hpp"
 
 namespace megba {
-
-// Which kernels form the local E Cinv E^T x product of a PCG iteration.
-enum class SchurPath {
-  Lds,           // kSchurFusedLds + row reduce (single pass, LDS accumulator)
-  LdsRecompute,  // kSchurFusedLdsRc: Lds with the BAL J rebuilt per edge
-  FusedEtx,      // kEtxCinvFused, then E w (default)
-  Separate,      // E^T x, Cinv, E w as separate passes
-  OnePass,       // kSchurFused (MEGBA_FUSED)
-};
-
-// What one PCG iteration launches.  Resolved once at the first solve
-// (GpuEngine::resolvePlan) and immutable afterwards: the captured hipGraph
-// of the PCG body depends on every field.
-struct PcgPlan {
-  SchurPath path = SchurPath::FusedEtx;
-  bool rotatedBody = true;         // four-kernel body (else seven-kernel)
-  bool productReadsPad = true;     // the product reads dXPad_, not p
-  bool mergeReduceBApply = false;  // kLdsReduceBApplyDot ends the product
-};
 
 // ===========================================================================
 // Host engine
@@ -201,8 +161,7 @@ class GpuEngine final : public Engine<T> {
       for (int64_t i = 0; i < nc_; ++i) h[i] = (T)prob.cams[i];
       for (int64_t i = 0; i < np_; ++i) h[nc_ + i] = (T)prob.pts[i];
       up(dParams_, h.data(), dim_);
-      HIP_CHECK(hipMemcpyAsync(dParamsBak_, dParams_, dim_ * sizeof(T),
-                               hipMemcpyDeviceToDevice, stream_));
+      copyD2D(dParamsBak_, dParams_, dim_);
     }
 
     // Residual / Jacobian double-buffer (current + accepted).
@@ -224,8 +183,8 @@ class GpuEngine final : public Engine<T> {
     dHllInv_ = dalloc<T>((int64_t)npt_ * PP);
     dDeltaX_ = dalloc<T>(dim_);
     dDeltaXBak_ = dalloc<T>(dim_);
-    HIP_CHECK(hipMemsetAsync(dDeltaX_, 0, dim_ * sizeof(T), stream_));
-    HIP_CHECK(hipMemsetAsync(dDeltaXBak_, 0, dim_ * sizeof(T), stream_));
+    zero(dDeltaX_, dim_);
+    zero(dDeltaXBak_, dim_);
 
     // PCG workspace.
     dP_ = dalloc<T>(nc_);
@@ -235,11 +194,11 @@ class GpuEngine final : public Engine<T> {
     dV_ = dalloc<T>(nc_);
     dXBak_ = dalloc<T>(nc_);
     dXBakPrev_ = dalloc<T>(nc_);
-    HIP_CHECK(hipMemsetAsync(dXBak_, 0, nc_ * sizeof(T), stream_));
-    HIP_CHECK(hipMemsetAsync(dXBakPrev_, 0, nc_ * sizeof(T), stream_));
+    zero(dXBak_, nc_);
+    zero(dXBakPrev_, nc_);
     dW_ = dalloc<T>(np_);
     dTemp_ = dalloc<T>(np_);
-    HIP_CHECK(hipMemsetAsync(dW_, 0, np_ * sizeof(T), stream_));
+    zero(dW_, np_);
 
     // Partial-sum scratch: big enough for both the fixed-shape two-pass
     // reductions (kRedBlocks) and the fused B-apply+dot grid over nc_.
@@ -317,35 +276,23 @@ class GpuEngine final : public Engine<T> {
     freshCur_ = true;
     if (customFwd_) return forwardCustom();
     zeroScalar();
-    if (analytical_) {
-      // compile the analytical launch only for its valid dims
-      if constexpr (CD == 9 && PD == 3 && RD == 2)
-        hipLaunchKernelGGL(kForwardAnalytical<T>, dim3(gridFor(nL_)),
-                           dim3(kBlk), 0, stream_, nL_, dCamOf_, dPtOf_,
-                           dParams_, ncam_, dMeas_, dCamFixed_, dPtFixed_,
-                           dR_[cur_], dJc_[cur_], dJp_[cur_], scalarPtr(),
-                           lossKind_, lossD2_);
-    } else {
-      constexpr int LANES = (GW + 2) / 3;
-      bool launched = false;
-      if constexpr (CD == 9 && PD == 3 && RD == 2) {
-        if (knobs_.fwdVS) {
-          hipLaunchKernelGGL(kForwardVS<T>, dim3(gridFor(nL_ * 4)),
-                             dim3(kBlk), 0, stream_, nL_, dCamOf_, dPtOf_,
-                             dParams_, ncam_, dMeas_, dCamFixed_, dPtFixed_,
-                             dR_[cur_], dJc_[cur_], dJp_[cur_], scalarPtr(),
-                             lossKind_, lossD2_);
-          launched = true;
-        }
-      }
-      if (!launched)
-        hipLaunchKernelGGL((kForward<T, CD, PD, RD>),
-                           dim3(gridFor(nL_ * LANES)), dim3(kBlk), 0, stream_,
-                           nL_, dCamOf_, dPtOf_, dParams_, ncam_, dMeas_,
-                           dCamFixed_, dPtFixed_, dR_[cur_], dJc_[cur_],
-                           dJp_[cur_], scalarPtr(), lossKind_, lossD2_,
-                           dIntr_);
+    // `lanes` threads per observation; kForward alone takes the intrinsics
+    const auto fwd = [&](auto kernel, int lanes, auto... intr) {
+      launchN(kernel, nL_ * lanes, nL_, dCamOf_, dPtOf_, dParams_, ncam_,
+              dMeas_, dCamFixed_, dPtFixed_, dR_[cur_], dJc_[cur_], dJp_[cur_],
+              scalarPtr(), lossKind_, lossD2_, intr...);
+    };
+    // the analytical and value-share kernels exist for the BAL dims only
+    // (the constructor refuses analytical_ on any other dims)
+    bool launched = false;
+    if constexpr (kBalDims) {
+      launched = analytical_ || knobs_.fwdVS;
+      if (analytical_)
+        fwd(kForwardAnalytical<T>, 1);
+      else if (knobs_.fwdVS)
+        fwd(kForwardVS<T>, 4);
     }
+    if (!launched) fwd(kForward<T, CD, PD, RD>, (GW + 2) / 3, dIntr_);
     if (hasPriors_) priorForward();
     return globalScalar(ncclSum);
   }
@@ -364,22 +311,19 @@ class GpuEngine final : public Engine<T> {
   // linearisation point (kBalSnapshot), read by kSchurFusedLdsRc alone.
   void snapshotAccepted() {
     if constexpr (kBalDims)
-      hipLaunchKernelGGL(kBalSnapshot<T>, dim3(gridFor((int64_t)ncam_ + npL_)),
-                         dim3(kBlk), 0, stream_, ncam_, ptLo_, npL_, dParams_,
-                         dCamRow_, rcCamStride(), dPtAcc_);
+      launchN(kBalSnapshot<T>, (int64_t)ncam_ + npL_, ncam_, ptLo_, npL_,
+              dParams_, dCamRow_, rcCamStride(), dPtAcc_);
   }
 
   // Point the device slots at the accepted (bak) buffer set.
   void updateJSlots() {
     const int bak = cur_ ^ 1;
-    hipLaunchKernelGGL(kSetPtrSlots<T>, dim3(1), dim3(1), 0, stream_,
-                       dJSlots_, dJc_[bak], dJp_[bak], dR_[bak]);
+    launch(kSetPtrSlots<T>, 1, 1, 0, dJSlots_, dJc_[bak], dJp_[bak], dR_[bak]);
   }
 
   double forwardCustom() {
-    hipLaunchKernelGGL((kGatherLeaves<T, CD, PD>), dim3(gridFor(nL_)),
-                       dim3(kBlk), 0, stream_, nL_, dCamOf_, dPtOf_, dParams_,
-                       ncam_, dLeaf_);
+    launchN(kGatherLeaves<T, CD, PD>, nL_, nL_, dCamOf_, dPtOf_, dParams_,
+            ncam_, dLeaf_);
     sync();  // JetVector ops run on the null stream
     std::vector<JetVec<T>> camL, ptL, ms, res;
     for (int k = 0; k < CD; ++k)
@@ -398,16 +342,14 @@ class GpuEngine final : public Engine<T> {
                       res[r].N == GW && res[r].onGpu,
                   "custom residual must be a dense GPU JetVector "
                   "(N=camDim+ptDim)");
-      hipLaunchKernelGGL((kRepackRes<T, CD, PD, RD>), dim3(gridFor(nL_)),
-                         dim3(kBlk), 0, stream_, nL_, r, res[r].value->ptr,
-                         res[r].grad->ptr, dCamOf_, dPtOf_, dCamFixed_,
-                         dPtFixed_, dR_[cur_], dJc_[cur_], dJp_[cur_]);
+      launchN(kRepackRes<T, CD, PD, RD>, nL_, nL_, r, res[r].value->ptr,
+              res[r].grad->ptr, dCamOf_, dPtOf_, dCamFixed_, dPtFixed_,
+              dR_[cur_], dJc_[cur_], dJp_[cur_]);
     }
     if (lossKind_) {
       zeroScalar();
-      hipLaunchKernelGGL((kChi2Loss<T, RD>), dim3(gridFor(nL_)), dim3(kBlk),
-                         0, stream_, nL_, dR_[cur_], lossKind_, lossD2_,
-                         scalarPtr());
+      launchN(kChi2Loss<T, RD>, nL_, nL_, dR_[cur_], lossKind_, lossD2_,
+              scalarPtr());
     } else {
       reduceDetAsync(dR_[cur_], dR_[cur_], nL_ * RD, ROp::SumSq, scalarPtr());
     }
@@ -418,25 +360,19 @@ class GpuEngine final : public Engine<T> {
 
   void buildLinearSystem() override {
     const int bak = cur_ ^ 1;
-    HIP_CHECK(hipMemsetAsync(dHpp_, 0, (int64_t)ncam_ * CC * sizeof(T), stream_));
-    HIP_CHECK(hipMemsetAsync(dHll_ + (int64_t)ptLo_ * PP, 0,
-                             (int64_t)npL_ * PP * sizeof(T), stream_));
-    HIP_CHECK(hipMemsetAsync(dG_, 0, nc_ * sizeof(T), stream_));
-    HIP_CHECK(hipMemsetAsync(dG_ + nc_ + (int64_t)ptLo_ * PD, 0,
-                             (int64_t)npL_ * PD * sizeof(T), stream_));
+    zero(dHpp_, (int64_t)ncam_ * CC);
+    zero(shard(dHll_, PP), (int64_t)npL_ * PP);
+    zero(dG_, nc_);
+    zero(shard(dG_ + nc_, PD), (int64_t)npL_ * PD);
     dispatchAssemble(bak);
-    if (!implicit_)
-      dispatchBool(weighted(), [&](auto weightedTag) {
-        hipLaunchKernelGGL(
-            (kFinalizeCam<T, CD, PD, RD, decltype(weightedTag)::value>),
-            dim3(gridFor(nL_)), dim3(kBlk), 0, stream_, nL_, dSlab_, dHplCam_);
-      });
-    else
-      dispatchBool(weighted(), [&](auto weightedTag) {
-        hipLaunchKernelGGL(
-            (kFinalizeCamImpPk<T, CD, PD, RD, decltype(weightedTag)::value>),
-            dim3(gridFor(nL_)), dim3(kBlk), 0, stream_, nL_, dSlab_, dJCamPk_);
-      });
+    dispatchBool(weighted(), [&](auto weightedTag) {
+      constexpr bool HI = decltype(weightedTag)::value;
+      if (!implicit_)
+        launchN(kFinalizeCam<T, CD, PD, RD, HI>, nL_, nL_, dSlab_, dHplCam_);
+      else
+        launchN(kFinalizeCamImpPk<T, CD, PD, RD, HI>, nL_, nL_, dSlab_,
+                dJCamPk_);
+    });
     // Only the small camera-side quantities cross ranks (the reference
     // allreduced Hpp, Hll AND g, its site A1).
     allreduce(dHpp_, (int64_t)ncam_ * CC, ncclSum);
@@ -447,61 +383,33 @@ class GpuEngine final : public Engine<T> {
     sync();
   }
 
-  void backupParams() override {
-    HIP_CHECK(hipMemcpyAsync(dParamsBak_, dParams_, dim_ * sizeof(T),
-                             hipMemcpyDeviceToDevice, stream_));
-  }
-  void rollbackParams() override {
-    HIP_CHECK(hipMemcpyAsync(dParams_, dParamsBak_, dim_ * sizeof(T),
-                             hipMemcpyDeviceToDevice, stream_));
-  }
+  void backupParams() override { copyD2D(dParamsBak_, dParams_, dim_); }
+  void rollbackParams() override { copyD2D(dParams_, dParamsBak_, dim_); }
   void backupGDx() override {
-    HIP_CHECK(hipMemcpyAsync(dDeltaXBak_, dDeltaX_, dim_ * sizeof(T),
-                             hipMemcpyDeviceToDevice, stream_));
-    HIP_CHECK(hipMemcpyAsync(dGBak_, dG_, dim_ * sizeof(T),
-                             hipMemcpyDeviceToDevice, stream_));
+    copyD2D(dDeltaXBak_, dDeltaX_, dim_);
+    copyD2D(dGBak_, dG_, dim_);
   }
   void rollbackGDx() override {
-    HIP_CHECK(hipMemcpyAsync(dDeltaX_, dDeltaXBak_, dim_ * sizeof(T),
-                             hipMemcpyDeviceToDevice, stream_));
-    HIP_CHECK(hipMemcpyAsync(dG_, dGBak_, dim_ * sizeof(T),
-                             hipMemcpyDeviceToDevice, stream_));
+    copyD2D(dDeltaX_, dDeltaXBak_, dim_);
+    copyD2D(dG_, dGBak_, dim_);
   }
 
   void processDiag(double region) override {
     const T f = T(1) + T(1) / (T)region;
-    hipLaunchKernelGGL((kDamp<T, CD>), dim3(gridFor((int64_t)ncam_ * CC)),
-                       dim3(kBlk), 0, stream_, (int64_t)ncam_ * CC, dHpp_,
-                       dHppD_, f, dCamFixed_);
-    hipLaunchKernelGGL((kDamp<T, PD>), dim3(gridFor((int64_t)npL_ * PP)),
-                       dim3(kBlk), 0, stream_, (int64_t)npL_ * PP,
-                       dHll_ + (int64_t)ptLo_ * PP, dHllD_ + (int64_t)ptLo_ * PP,
-                       f, dPtFixed_ ? dPtFixed_ + ptLo_ : nullptr);
+    launchN(kDamp<T, CD>, (int64_t)ncam_ * CC, (int64_t)ncam_ * CC, dHpp_,
+            dHppD_, f, dCamFixed_);
+    launchN(kDamp<T, PD>, (int64_t)npL_ * PP, (int64_t)npL_ * PP,
+            shard(dHll_, PP), shard(dHllD_, PP), f,
+            dPtFixed_ ? dPtFixed_ + ptLo_ : nullptr);
   }
 
   int solveLinear(const SolverOptionPCG& opt) override {
     // Block inverses (preconditioner replicated; Cinv on the local shard).
     HIP_CHECK(hipMemsetAsync(dFail_, 0, 2 * sizeof(int), stream_));
-    hipLaunchKernelGGL((kInvert<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                       stream_, ncam_, dHppD_, dHppInv_, dFail_);
-    hipLaunchKernelGGL((kInvert<T, PD>), dim3(gridFor(npL_)), dim3(kBlk), 0,
-                       stream_, npL_, dHllD_ + (int64_t)ptLo_ * PP,
-                       dHllInv_ + (int64_t)ptLo_ * PP, dFail_);
     int fail[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(fail, dFail_, 2 * sizeof(int),
-                             hipMemcpyDeviceToHost, stream_));
-    sync();
+    invertBlocks(kInvert<T, CD>, kInvert<T, PD>, fail);
     if (fail[0]) {
-      hipLaunchKernelGGL((kInvertJitter<T, CD>), dim3(gridFor(ncam_)),
-                         dim3(kBlk), 0, stream_, ncam_, dHppD_, dHppInv_,
-                         dFail_);
-      hipLaunchKernelGGL((kInvertJitter<T, PD>), dim3(gridFor(npL_)),
-                         dim3(kBlk), 0, stream_, npL_,
-                         dHllD_ + (int64_t)ptLo_ * PP,
-                         dHllInv_ + (int64_t)ptLo_ * PP, dFail_);
-      HIP_CHECK(hipMemcpyAsync(fail, dFail_, 2 * sizeof(int),
-                               hipMemcpyDeviceToHost, stream_));
-      sync();
+      invertBlocks(kInvertJitter<T, CD>, kInvertJitter<T, PD>, fail);
       MEGBA_CHECK(!fail[1], "singular Hessian block");
     }
 
@@ -510,14 +418,12 @@ class GpuEngine final : public Engine<T> {
     const T* gp = dG_ + nc_;
     // v = gc/world - E Cinv gp  (partial, then the CD*ncam allreduce)
     cinvThenEx(gp, dV_);
-    hipLaunchKernelGGL(kVMake<T>, dim3(gridFor(nc_)), dim3(kBlk), 0, stream_,
-                       nc_, gc, T(1) / T(world_), dV_);
+    launchN(kVMake<T>, nc_, nc_, gc, T(1) / T(world_), dV_);
     allreduce(dV_, nc_, ncclSum);
     // Warm start: x = deltaX camera part (in place in dDeltaX_).
     T* x = dDeltaX_;
     schurApply({x, false}, dQ_, /*withDot=*/false);
-    hipLaunchKernelGGL(kSub<T>, dim3(gridFor(nc_)), dim3(kBlk), 0, stream_, nc_,
-                       dV_, dQ_, dRr_);
+    launchN(kSub<T>, nc_, nc_, dV_, dQ_, dRr_);
 
     // The loop body is value-uniform (beta/alpha live on-device; the first
     // iteration gets beta = rho/INF = 0 against a zeroed p), so it is
@@ -526,14 +432,13 @@ class GpuEngine final : public Engine<T> {
     // control flow.  Refuse semantics are preserved with a two-deep x backup
     // (the body runs speculatively; on refuse x is restored to the value two
     // updates back, exactly what the reference's pre-update check restores).
-    HIP_CHECK(hipMemsetAsync(dP_, 0, nc_ * sizeof(T), stream_));
-    hipLaunchKernelGGL(kSetScalar, dim3(1), dim3(1), 0, stream_, slotRhoPrev(),
-                       INFINITY);
+    zero(dP_, nc_);
+    launch(kSetScalar, 1, 1, 0, slotRhoPrev(), INFINITY);
     // Rotated body: the first z = Binv r and rho partials come from here,
     // every later one from the tail of the previous body.
     if (plan_->rotatedBody)
-      hipLaunchKernelGGL((kPrecondRho<T, CD>), dim3(precondGrid()), dim3(kBlk),
-                         0, stream_, ncam_, dHppInv_, dRr_, dZ_, dPart_);
+      launch(kPrecondRho<T, CD>, precondGrid(), kBlk, 0, ncam_, dHppInv_,
+             dRr_, dZ_, dPart_);
     int n = 0;
     double rho = 0.0, rhoMin = INFINITY;
     bool done = false;
@@ -559,8 +464,7 @@ class GpuEngine final : public Engine<T> {
         }
         rho = readScalar(slotRho());
         if (rho > opt.refuseRatio * rhoMin) {
-          HIP_CHECK(hipMemcpyAsync(x, dXBakPrev_, nc_ * sizeof(T),
-                                   hipMemcpyDeviceToDevice, stream_));
+          copyD2D(x, dXBakPrev_, nc_);
           break;
         }
         rhoMin = rhoMin < rho ? rhoMin : rho;
@@ -570,44 +474,22 @@ class GpuEngine final : public Engine<T> {
     }
     // Back-substitution: deltaX_p = Cinv (g_p - E^T x), fully local.
     spmvEtx({x, false}, dTemp_);
-    hipLaunchKernelGGL((kBackSub<T, PD>), dim3(gridFor(npL_)), dim3(kBlk), 0,
-                       stream_, npL_, dHllInv_ + (int64_t)ptLo_ * PP,
-                       gp + (int64_t)ptLo_ * PD, dTemp_ + (int64_t)ptLo_ * PD,
-                       dDeltaX_ + nc_ + (int64_t)ptLo_ * PD);
+    launchN(kBackSub<T, PD>, npL_, npL_, shard(dHllInv_, PP), shard(gp, PD),
+            shard(dTemp_, PD), shard(dDeltaX_ + nc_, PD));
     sync();
     return n;
   }
 
   double deltaXL2() override {
-    const double camSS = reduceDet(dDeltaX_, dDeltaX_, nc_, ROp::SumSq);
-    reduceDetAsync(dDeltaX_ + nc_ + (int64_t)ptLo_ * PD,
-                   dDeltaX_ + nc_ + (int64_t)ptLo_ * PD, (int64_t)npL_ * PD,
-                   ROp::SumSq, scalarPtr());
-    return std::sqrt(camSS + globalScalar(ncclSum));
+    return std::sqrt(reduceVec(dDeltaX_, ROp::SumSq));
   }
-  double xL2() override {
-    const double camSS = reduceDet(dParams_, dParams_, nc_, ROp::SumSq);
-    reduceDetAsync(dParams_ + nc_ + (int64_t)ptLo_ * PD,
-                   dParams_ + nc_ + (int64_t)ptLo_ * PD, (int64_t)npL_ * PD,
-                   ROp::SumSq, scalarPtr());
-    return std::sqrt(camSS + globalScalar(ncclSum));
-  }
-  double gInf() override {
-    const double camMax = reduceDet(dG_, dG_, nc_, ROp::AbsMax);
-    reduceDetAsync(dG_ + nc_ + (int64_t)ptLo_ * PD,
-                   dG_ + nc_ + (int64_t)ptLo_ * PD, (int64_t)npL_ * PD,
-                   ROp::AbsMax, scalarPtr());
-    const double ptMax = globalScalar(ncclMax);
-    return camMax > ptMax ? camMax : ptMax;
-  }
+  double xL2() override { return std::sqrt(reduceVec(dParams_, ROp::SumSq)); }
+  double gInf() override { return reduceVec(dG_, ROp::AbsMax); }
 
   void updateParams() override {
-    hipLaunchKernelGGL(kAddAssign<T>, dim3(gridFor(nc_)), dim3(kBlk), 0,
-                       stream_, nc_, dDeltaX_, dParams_);
-    hipLaunchKernelGGL(kAddAssign<T>, dim3(gridFor((int64_t)npL_ * PD)),
-                       dim3(kBlk), 0, stream_, (int64_t)npL_ * PD,
-                       dDeltaX_ + nc_ + (int64_t)ptLo_ * PD,
-                       dParams_ + nc_ + (int64_t)ptLo_ * PD);
+    launchN(kAddAssign<T>, nc_, nc_, dDeltaX_, dParams_);
+    launchN(kAddAssign<T>, (int64_t)npL_ * PD, (int64_t)npL_ * PD,
+            shard(dDeltaX_ + nc_, PD), shard(dParams_ + nc_, PD));
   }
 
   double rhoDenominator(double chi2Backup) override {
@@ -616,45 +498,30 @@ class GpuEngine final : public Engine<T> {
     if (implicit_) {
       // packed accepted J + padded deltaX camera vector
       padX(dDeltaX_, xPadDst());
-      hipLaunchKernelGGL((kRhoDenomPk<T, CD, PD, RD>), dim3(gridFor(nL_)),
-                         dim3(kBlk), 0, stream_, nL_, dCamOf_, dPtOf_,
-                         dR_[bak], dJPk_, dXPad_, dDeltaX_ + nc_,
-                         scalarPtr(), lossKind_, lossD2_);
+      launchN(kRhoDenomPk<T, CD, PD, RD>, nL_, nL_, dCamOf_, dPtOf_, dR_[bak],
+              dJPk_, dXPad_, dDeltaX_ + nc_, scalarPtr(), lossKind_, lossD2_);
     } else {
-      hipLaunchKernelGGL((kRhoDenom<T, CD, PD, RD>), dim3(gridFor(nL_)),
-                         dim3(kBlk), 0, stream_, nL_, dCamOf_, dPtOf_,
-                         dR_[bak], dJc_[bak], dJp_[bak], dDeltaX_,
-                         dDeltaX_ + nc_, scalarPtr(), lossKind_, lossD2_);
+      launchN(kRhoDenom<T, CD, PD, RD>, nL_, nL_, dCamOf_, dPtOf_, dR_[bak],
+              dJc_[bak], dJp_[bak], dDeltaX_, dDeltaX_ + nc_, scalarPtr(),
+              lossKind_, lossD2_);
     }
     if (hasPriors_) priorRho();
     return globalScalar(ncclSum) - chi2Backup;
   }
 
   void getParams(double* cams, double* pts) override {
-    std::vector<T> hc(nc_);
-    HIP_CHECK(hipMemcpy(hc.data(), dParams_, nc_ * sizeof(T),
-                        hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < nc_; ++i) cams[i] = (double)hc[i];
+    downTo(cams, dParams_, nc_);
+    const T* src = dParams_ + nc_;
     if (world_ > 1 && (hasComm_ || hostAr_)) {
       // point shards: zero the non-local entries, allreduce-sum.
       if (!dPtMerge_) dPtMerge_ = dalloc<T>(np_);
-      T* tmp = dPtMerge_;
-      HIP_CHECK(hipMemsetAsync(tmp, 0, np_ * sizeof(T), stream_));
-      HIP_CHECK(hipMemcpyAsync(tmp + (int64_t)ptLo_ * PD,
-                               dParams_ + nc_ + (int64_t)ptLo_ * PD,
-                               (int64_t)npL_ * PD * sizeof(T),
-                               hipMemcpyDeviceToDevice, stream_));
-      allreduce(tmp, np_, ncclSum);
+      zero(dPtMerge_, np_);
+      copyD2D(shard(dPtMerge_, PD), shard(src, PD), (int64_t)npL_ * PD);
+      allreduce(dPtMerge_, np_, ncclSum);
       sync();
-      std::vector<T> h(np_);
-      HIP_CHECK(hipMemcpy(h.data(), tmp, np_ * sizeof(T), hipMemcpyDeviceToHost));
-      for (int64_t i = 0; i < np_; ++i) pts[i] = (double)h[i];
-      return;
+      src = dPtMerge_;
     }
-    std::vector<T> h(np_);
-    HIP_CHECK(hipMemcpy(h.data(), dParams_ + nc_, np_ * sizeof(T),
-                        hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < np_; ++i) pts[i] = (double)h[i];
+    downTo(pts, src, np_);
   }
 
   DenseDump dump() const override {
@@ -718,10 +585,10 @@ class GpuEngine final : public Engine<T> {
     upCast(s.info, h.info.data(), h.info.size());
     for (int b = 0; b < 2; ++b) {
       s.r[b] = dalloc<T>(m * D);
-      HIP_CHECK(hipMemsetAsync(s.r[b], 0, m * D * sizeof(T), stream_));
+      zero(s.r[b], m * D);
       if (jw > 0) {
         s.J[b] = dalloc<T>(m * jw);
-        HIP_CHECK(hipMemsetAsync(s.J[b], 0, m * jw * sizeof(T), stream_));
+        zero(s.J[b], m * jw);
       }
     }
   }
@@ -767,9 +634,8 @@ class GpuEngine final : public Engine<T> {
   void priorForward() {
     forEachPrior([&](auto kind, auto, const DevPrior& s, const PriorSite& at) {
       const PriorView<T> p = s.view(cur_);
-      hipLaunchKernelGGL((kPriorForward<T, decltype(kind)>),
-                         dim3(priorRedGrid(p.m)), dim3(kBlk), 0, stream_, p.m,
-                         p.idx, p.mean, p.info, p.r, p.J, at.x, at.acc);
+      launch(kPriorForward<T, decltype(kind)>, priorRedGrid(p.m), kBlk, 0,
+             p.m, p.idx, p.mean, p.info, p.r, p.J, at.x, at.acc);
     });
   }
 
@@ -780,10 +646,9 @@ class GpuEngine final : public Engine<T> {
       using Kind = decltype(kind);
       constexpr bool PER_ROW = decltype(perRow)::value;
       const PriorView<T> p = s.view(cur_ ^ 1);
-      hipLaunchKernelGGL((kPriorAssemble<T, Kind, PER_ROW>),
-                         dim3(gridFor(PER_ROW ? p.m * Kind::ROWS : p.m)),
-                         dim3(kBlk), 0, stream_, p.m, p.idx, p.info, p.r, p.J,
-                         at.fixed, at.H, at.g);
+      launchN(kPriorAssemble<T, Kind, PER_ROW>,
+              PER_ROW ? p.m * Kind::ROWS : p.m, p.m, p.idx, p.info, p.r, p.J,
+              at.fixed, at.H, at.g);
     });
   }
 
@@ -791,9 +656,8 @@ class GpuEngine final : public Engine<T> {
   void priorRho() {
     forEachPrior([&](auto kind, auto, const DevPrior& s, const PriorSite& at) {
       const PriorView<T> p = s.view(cur_ ^ 1);
-      hipLaunchKernelGGL((kPriorRho<T, decltype(kind)>),
-                         dim3(priorRedGrid(p.m)), dim3(kBlk), 0, stream_, p.m,
-                         p.idx, p.info, p.r, p.J, at.fixed, at.dx, at.acc);
+      launch(kPriorRho<T, decltype(kind)>, priorRedGrid(p.m), kBlk, 0, p.m,
+             p.idx, p.info, p.r, p.J, at.fixed, at.dx, at.acc);
     });
   }
 
@@ -804,33 +668,28 @@ class GpuEngine final : public Engine<T> {
            (implicit_ ? PR : 0);
   }
   void dispatchAssemble(int bak) {
-    auto launch = [&](auto weightedTag, auto explTag) {
+    auto assemble = [&](auto weightedTag, auto explTag) {
       constexpr bool HI = decltype(weightedTag)::value;
       constexpr bool EX = decltype(explTag)::value;
-      hipLaunchKernelGGL((kAssembleEdge<T, CD, PD, RD, HI, EX>),
-                         dim3(gridFor(nL_)), dim3(kBlk), 0, stream_, nL_,
-                         dCamOf_, dPtOf_, dR_[bak], dJc_[bak], dJp_[bak],
-                         dInfo_, dHll_, dHpl_, dG_, ncam_, dCamPos_, dSlab_,
-                         lossKind_, lossD2_, dJPk_);
+      launchN(kAssembleEdge<T, CD, PD, RD, HI, EX>, nL_, nL_, dCamOf_, dPtOf_,
+              dR_[bak], dJc_[bak], dJp_[bak], dInfo_, dHll_, dHpl_, dG_, ncam_,
+              dCamPos_, dSlab_, lossKind_, lossD2_, dJPk_);
       if (nChunks_ > 0) {
         if constexpr (std::is_same<T, double>::value && CD == 9 && PD == 3 &&
                       RD == 2) {
           if (knobs_.mfma) {
-            hipLaunchKernelGGL((kAssembleCamMfma<T, CD, PD, RD, HI, EX>),
-                               dim3(nChunks_), dim3(64), 0, stream_,
-                               nChunks_, dChCam_, dChLo_, dChHi_, dSlab_,
-                               dHpp_, dG_);
+            launch(kAssembleCamMfma<T, CD, PD, RD, HI, EX>, nChunks_, 64, 0,
+                   nChunks_, dChCam_, dChLo_, dChHi_, dSlab_, dHpp_, dG_);
             return;
           }
         }
-        hipLaunchKernelGGL((kAssembleCam<T, CD, PD, RD, HI, EX>),
-                           dim3(nChunks_), dim3(128), 0, stream_, nChunks_,
-                           dChCam_, dChLo_, dChHi_, dSlab_, dHpp_, dG_);
+        launch(kAssembleCam<T, CD, PD, RD, HI, EX>, nChunks_, 128, 0, nChunks_,
+               dChCam_, dChLo_, dChHi_, dSlab_, dHpp_, dG_);
       }
     };
     dispatchBool(weighted(), [&](auto weightedTag) {
       dispatchBool(!implicit_,
-                   [&](auto explTag) { launch(weightedTag, explTag); });
+                   [&](auto explTag) { assemble(weightedTag, explTag); });
     });
   }
   // f(tag) with a runtime bool as an integral_constant tag.
@@ -838,6 +697,29 @@ class GpuEngine final : public Engine<T> {
   static decltype(auto) dispatchBool(bool b, F&& f) {
     if (b) return f(std::true_type{});
     return f(std::false_type{});
+  }
+  // Every kernel launch goes through these two: on stream_, and for a kernel
+  // over n items gridFor(n) blocks of kBlk threads without dynamic LDS.
+  template <typename K, typename... A>
+  void launch(K kernel, int grid, int block, size_t ldsBytes, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), ldsBytes, stream_,
+                       args...);
+  }
+  template <typename K, typename... A>
+  void launchN(K kernel, int64_t n, A... args) {
+    launch(kernel, gridFor(n), kBlk, 0, args...);
+  }
+  // This rank's point shard of a point-indexed array of `width` per point.
+  template <typename U>
+  U* shard(U* base, int width) const {
+    return base + (int64_t)ptLo_ * width;
+  }
+  void zero(T* p, int64_t n) {
+    HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(T), stream_));
+  }
+  void copyD2D(T* dst, const T* src, int64_t n) {
+    HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice,
+                             stream_));
   }
   template <typename U>
   U* dalloc(int64_t n) {
@@ -865,10 +747,15 @@ class GpuEngine final : public Engine<T> {
     if (n > 0)
       HIP_CHECK(hipMemcpy(dst, h.data(), n * sizeof(T), hipMemcpyHostToDevice));
   }
-  std::vector<double> down(const T* src, int64_t n) const {
+  void downTo(double* dst, const T* src, int64_t n) const {
     std::vector<T> h(n);
     HIP_CHECK(hipMemcpy(h.data(), (void*)src, n * sizeof(T), hipMemcpyDeviceToHost));
-    return std::vector<double>(h.begin(), h.end());
+    for (int64_t i = 0; i < n; ++i) dst[i] = (double)h[i];
+  }
+  std::vector<double> down(const T* src, int64_t n) const {
+    std::vector<double> o(n);
+    downTo(o.data(), src, n);
+    return o;
   }
   std::vector<double> transposeR(const std::vector<double>& v) const {
     std::vector<double> o(v.size());
@@ -943,33 +830,45 @@ class GpuEngine final : public Engine<T> {
     HIP_CHECK(hipMemcpy(buf, h.data(), n * sizeof(T), hipMemcpyHostToDevice));
   }
   void reduceDetAsync(const T* a, const T* b, int64_t n, ROp op, double* out) {
-    const auto launch = [&](auto opTag) {
+    const auto reduce = [&](auto opTag) {
       constexpr ROp OP = decltype(opTag)::value;
-      hipLaunchKernelGGL((kRedPartial<T, OP>), dim3(kRedBlocks), dim3(kBlk), 0,
-                         stream_, a, b, n, dPart_);
-      hipLaunchKernelGGL((kRedFinal<OP>), dim3(1), dim3(kBlk), 0, stream_,
-                         dPart_, kRedBlocks, out);
+      launch(kRedPartial<T, OP>, kRedBlocks, kBlk, 0, a, b, n, dPart_);
+      launch(kRedFinal<OP>, 1, kBlk, 0, dPart_, kRedBlocks, out);
     };
     switch (op) {
-      case ROp::Dot: launch(std::integral_constant<ROp, ROp::Dot>{}); break;
-      case ROp::SumSq: launch(std::integral_constant<ROp, ROp::SumSq>{}); break;
-      case ROp::AbsMax: launch(std::integral_constant<ROp, ROp::AbsMax>{}); break;
+      case ROp::Dot: reduce(std::integral_constant<ROp, ROp::Dot>{}); break;
+      case ROp::SumSq: reduce(std::integral_constant<ROp, ROp::SumSq>{}); break;
+      case ROp::AbsMax: reduce(std::integral_constant<ROp, ROp::AbsMax>{}); break;
     }
   }
   double reduceDet(const T* a, const T* b, int64_t n, ROp op) {
     reduceDetAsync(a, b, n, op, scalarPtr());
     return readScalar(scalarPtr());
   }
+  // Sum of squares or abs-max of a dim_ vector: the replicated camera part
+  // here, this rank's point shard combined across the ranks.
+  double reduceVec(const T* v, ROp op) {
+    const double cam = reduceDet(v, v, nc_, op);
+    const T* pts = shard(v + nc_, PD);
+    reduceDetAsync(pts, pts, (int64_t)npL_ * PD, op, scalarPtr());
+    if (op == ROp::SumSq) return cam + globalScalar(ncclSum);
+    const double ptMax = globalScalar(ncclMax);
+    return cam > ptMax ? cam : ptMax;
+  }
+  // Block inverses of HppD and of this rank's HllD with the given kernel pair
+  // (kInvert, or kInvertJitter for the retry), then the failure flags.
+  template <typename KC, typename KP>
+  void invertBlocks(KC camKernel, KP ptKernel, int fail[2]) {
+    launchN(camKernel, ncam_, ncam_, dHppD_, dHppInv_, dFail_);
+    launchN(ptKernel, npL_, npL_, shard(dHllD_, PP), shard(dHllInv_, PP),
+            dFail_);
+    HIP_CHECK(hipMemcpyAsync(fail, dFail_, 2 * sizeof(int),
+                             hipMemcpyDeviceToHost, stream_));
+    sync();
+  }
   template <int D, int MODE>
   void blockMatVec(int nBlk, const T* A, const T* xv, T* yv) {
-    hipLaunchKernelGGL((kBlockDiagMatVec<T, D, MODE>),
-                       dim3(gridFor((int64_t)nBlk * D)), dim3(kBlk), 0, stream_,
-                       nBlk, A, xv, yv);
-  }
-  // w_local = Cinv * in_local  (pointers offset to the local shard)
-  void applyCinv(const T* in, T* out) {
-    blockMatVec<PD, 0>(npL_, dHllInv_ + (int64_t)ptLo_ * PP,
-                       in + (int64_t)ptLo_ * PD, out + (int64_t)ptLo_ * PD);
+    launchN(kBlockDiagMatVec<T, D, MODE>, (int64_t)nBlk * D, nBlk, A, xv, yv);
   }
   // The kernels of one PCG iteration.  Resolved once, at the first solve, and
   // never written again: the captured PCG graph bakes in what it selects.
@@ -978,108 +877,55 @@ class GpuEngine final : public Engine<T> {
     // MEGBA_TUNE_VERBOSE reports the tuner's choice (the tests read it
     // back), also when MEGBA_FUSED then overrides the product
     if (knobs_.tuneVerbose)
-      fprintf(stderr, "# schur path: %s\n",
-              tuned == SchurPath::Lds            ? "lds"
-              : tuned == SchurPath::LdsRecompute ? "lds-recompute"
-              : tuned == SchurPath::FusedEtx     ? "fused-etx"
-                                                 : "separate");
+      fprintf(stderr, "# schur path: %s\n", schurPathName(tuned));
     if (knobs_.tuneVerbose && tuned == SchurPath::LdsRecompute)
       fprintf(stderr, "# schur recompute gather: %s\n",
               rcStaged_ ? "staged" : "per-lane");
-    PcgPlan plan;
-    plan.path = knobs_.fused ? SchurPath::OnePass : tuned;
-    plan.rotatedBody = !knobs_.noPcgFuse;
-    // only the explicit separate-pass kSpmvEtx reads the unpadded vector
-    plan.productReadsPad = implicit_ || plan.path != SchurPath::Separate;
-    // row reduce, B-apply and dot in one kernel when nothing sits between
-    // them: LDS path, no long-run finishers, no collective
-    plan.mergeReduceBApply = plan.rotatedBody &&
-                             (plan.path == SchurPath::Lds ||
-                              plan.path == SchurPath::LdsRecompute) &&
-                             nLongPts_ == 0 && allreduceIsNoop();
-    return plan;
+    return makePcgPlan(tuned, knobs_, implicit_, nLongPts_, allreduceIsNoop());
   }
-  // One-time measured choice between the fused E^T x + Cinv window kernel
-  // and the separate-pass pipeline: which wins is problem-dependent
-  // (Venice wins fused in BOTH dtypes, final13682-fp32 wins separate —
-  // profiles/r02_gather_bands.md Exp 6), so unless an env override is
-  // set, time 3 local Schur applies each way on the real data and keep
-  // the faster.  Only the LOCAL part runs (no collective), so ranks may
-  // even pick differently without breaking lockstep: q partials are
-  // per-rank inputs to the allreduce either way.
-  //
-  // The LDS single-pass apply (schurFusedLdsEcE) is a third candidate when
-  // the camera vector fits the per-workgroup LDS limit (setupSchurLds).
-  // MEGBA_SCHUR_LDS forces it on when eligible (also the way problems below
-  // the tuning threshold reach it), MEGBA_NO_SCHUR_LDS removes it; forcing
-  // one of the two-pass variants (MEGBA_NO_ETXFUSE / MEGBA_ETXFUSE) leaves
-  // it out as well.
-  //
-  // The recomputed-J form of the LDS apply (SchurPath::LdsRecompute) is a
-  // fourth candidate under its own eligibility (setupSchurLds) and the same
-  // rules: MEGBA_SCHUR_RECOMPUTE forces it when eligible and then wins over
-  // MEGBA_SCHUR_LDS, MEGBA_NO_SCHUR_RECOMPUTE removes it, and where it is
-  // not eligible its forcing knob changes nothing.
+  // The device half of the choice that schur_plan.hpp describes: the first
+  // launch of each LDS candidate, and where nothing is forced 3 local Schur
+  // applies per candidate, timed on the real data.  Only the LOCAL part runs
+  // (no collective), so ranks may even pick differently without breaking
+  // lockstep: q partials are per-rank inputs to the allreduce either way.
   SchurPath chooseSchurPath() {
-    const SchurPath twoPass =
-        knobs_.noEtxFuse ? SchurPath::Separate : SchurPath::FusedEtx;
-    const bool twoPassForced = knobs_.noEtxFuse || knobs_.etxFuse;
-    const bool ldsForced = knobs_.schurLds;
-    const bool rcForced = knobs_.schurRecompute;
-    const bool tuning = !twoPassForced && nL_ >= 200000;
-    bool lds = ldsEligible_ && (!twoPassForced || ldsForced);
-    bool rc = rcEligible_ && (rcForced || (tuning && !ldsForced));
-    if (rc) {
-      // first launch outside any graph capture, as for the LDS apply below
+    // first launch happens here, outside any graph capture: a launch the
+    // runtime refuses (LDS size) drops the candidate instead of failing
+    const auto launches = [&](SchurPath path) {
       (void)hipGetLastError();
-      schurFusedLdsEcE({dDeltaX_, false}, dQ_, false, /*recompute=*/true);
-      if (hipGetLastError() != hipSuccess) rc = false;
-    }
-    if (rcForced && rc) return SchurPath::LdsRecompute;
-    // nothing to choose: a forced two-pass variant, or the launch-noise
-    // regime, where the default stays
-    if (!ldsForced && !tuning) return twoPass;
-    if (lds) {
-      // first launch happens here, outside any graph capture: a launch the
-      // runtime refuses (LDS size) drops the candidate instead of failing
-      (void)hipGetLastError();
-      schurFusedLdsEcE({dDeltaX_, false}, dQ_);
-      if (hipGetLastError() != hipSuccess) lds = false;
-    }
-    if (ldsForced) return lds ? SchurPath::Lds : twoPass;
+      localSchurEcE(path, {dDeltaX_, false}, dQ_);
+      return hipGetLastError() == hipSuccess;
+    };
+    // c.lds, c.rc: the LDS forms that are timed next to the two-pass paths
+    const SchurUntimed c = schurPathUntimed(
+        schurCandidates(knobs_, ldsEligible_, rcEligible_, nL_), launches);
+    if (c.path) return *c.path;
     hipEvent_t ev[2];
     HIP_CHECK(hipEventCreate(&ev[0]));
     HIP_CHECK(hipEventCreate(&ev[1]));
     float ms[4] = {0, 0, 0, 0};
-    const SchurPath variants[4] = {SchurPath::FusedEtx, SchurPath::Separate,
-                                   SchurPath::Lds, SchurPath::LdsRecompute};
-    const bool timed[4] = {true, true, lds, rc};
+    const bool timed[4] = {true, true, c.lds, c.rc};
     for (int variant = 0; variant < 4; ++variant) {
       if (!timed[variant]) continue;
       // warm-up then timed triple (dQ_/dWPad_/dTemp_ are scratch)
-      localSchurEcE(variants[variant], {dDeltaX_, false}, dQ_);
+      localSchurEcE(kTimedPaths[variant], {dDeltaX_, false}, dQ_);
       HIP_CHECK(hipEventRecord(ev[0], stream_));
       for (int k = 0; k < 3; ++k)
-        localSchurEcE(variants[variant], {dDeltaX_, false}, dQ_);
+        localSchurEcE(kTimedPaths[variant], {dDeltaX_, false}, dQ_);
       HIP_CHECK(hipEventRecord(ev[1], stream_));
       HIP_CHECK(hipEventSynchronize(ev[1]));
       HIP_CHECK(hipEventElapsedTime(&ms[variant], ev[0], ev[1]));
     }
-    const int best2 = ms[0] <= ms[1] ? 0 : 1;
-    const bool useLds = lds && ms[2] < ms[best2];
     if (knobs_.tuneVerbose)
       fprintf(stderr,
               "# schur autotune: fused-etx %.3f ms, separate %.3f ms, "
               "lds %.3f ms (3 applies each)\n",
-              ms[0], ms[1], lds ? ms[2] : -1.0f);
-    if (knobs_.tuneVerbose && rc)
+              ms[0], ms[1], c.lds ? ms[2] : -1.0f);
+    if (knobs_.tuneVerbose && c.rc)
       fprintf(stderr, "# schur recompute: %.3f ms (3 applies)\n", ms[3]);
     (void)hipEventDestroy(ev[0]);
     (void)hipEventDestroy(ev[1]);
-    // the recompute candidate only when it is the fastest of all
-    if (rc && ms[3] < ms[best2] && (!lds || ms[3] < ms[2]))
-      return SchurPath::LdsRecompute;
-    return useLds ? SchurPath::Lds : variants[best2];
+    return schurPathFromTimings(ms, c.lds, c.rc);
   }
 
   // f(impTag, infoTag) with this engine's (implicit_, hasInfo_) as
@@ -1111,9 +957,9 @@ class GpuEngine final : public Engine<T> {
       });
     return nullptr;
   }
-  // Dynamic LDS of kSchurFusedLdsRc: the accumulators, and for the staged
-  // instance one tile per wave behind them.
-  size_t rcLdsBytes(bool staged) const {
+  // Dynamic LDS of the LDS applies: the accumulators, and for the staged
+  // kSchurFusedLdsRc instance one tile per wave behind them.
+  size_t ldsBytes(bool staged = false) const {
     return staged ? (size_t)rcStagedLdsBytes(nc_, (int)sizeof(T),
                                              rcThreads_ / 64)
                   : (size_t)nc_ * sizeof(T);
@@ -1123,15 +969,13 @@ class GpuEngine final : public Engine<T> {
     if constexpr (kBalDims)
       dispatchBool(hasInfo_, [&](auto infoTag) {
         dispatchBool(rcStaged_, [&](auto stagedTag) {
-          hipLaunchKernelGGL(
-              (kSchurFusedLdsRc<T, decltype(infoTag)::value,
-                                decltype(stagedTag)::value>),
-              dim3(numCU_), dim3(rcThreads_), rcLdsBytes(rcStaged_), stream_,
-              nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_, dPtOf_,
-              dCamRow_, rcCamStride(), d.p + d.off, d.stride, dPtAcc_,
-              dCamFixed_, dPtFixed_,
-              (const T* const*)dJSlots_, dInfo_, lossKind_, lossD2_, dHllInv_,
-              dTemp_, (int)nc_, dLdsRows_);
+          launch(kSchurFusedLdsRc<T, decltype(infoTag)::value,
+                                  decltype(stagedTag)::value>,
+                 numCU_, rcThreads_, ldsBytes(rcStaged_), nWin_, dWinLo_,
+                 dWinHi_, dWinFlag_, nL_, dCamOf_, dPtOf_, dCamRow_,
+                 rcCamStride(), d.p + d.off, d.stride, dPtAcc_, dCamFixed_,
+                 dPtFixed_, (const T* const*)dJSlots_, dInfo_, lossKind_,
+                 lossD2_, dHllInv_, dTemp_, (int)nc_, dLdsRows_);
         });
       });
   }
@@ -1169,8 +1013,7 @@ class GpuEngine final : public Engine<T> {
   // loads than the wide rows, profiles/r09_rc_staged_gather.md).
   int rcCamStride() const { return rcStaged_ ? RcRow<T>::LEN : kBalCamRow; }
   void padX(const T* x, PadDst d) {
-    hipLaunchKernelGGL((kPadX<T, CD>), dim3(gridFor(ncam_)), dim3(kBlk), 0,
-                       stream_, ncam_, x, d.p, d.stride, d.off);
+    launchN(kPadX<T, CD>, ncam_, ncam_, x, d.p, d.stride, d.off);
   }
   // Common start of the window passes: the padded copy of x where the path
   // reads it unless it is ready, and a zeroed temp when >64-edge runs will
@@ -1180,17 +1023,18 @@ class GpuEngine final : public Engine<T> {
     if (!x.padReady) padX(x.v, padDstFor(path));
     if (nLongPts_ > 0 && path == SchurPath::LdsRecompute && rcStaged_)
       padX(x.v, xPadDst());
-    if (nLongPts_ > 0)
-      hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
-                         dim3(kBlk), 0, stream_, dTemp_ + (int64_t)ptLo_ * PD,
-                         (int64_t)npL_ * PD);
+    if (nLongPts_ > 0) zeroShard(dTemp_);
+  }
+  // Zero this rank's shard of a PD-wide point vector.
+  void zeroShard(T* v) {
+    launchN(kZeroRange<T>, (int64_t)npL_ * PD, shard(v, PD),
+            (int64_t)npL_ * PD);
   }
   // w_p = Cinv temp_p for the >64-edge points, into w at the given stride.
   void longRunW(T* w, int stride) {
     if (nLongPts_ > 0)
-      hipLaunchKernelGGL((kFusedLongW<T, PD>), dim3(gridFor(nLongPts_)),
-                         dim3(kBlk), 0, stream_, nLongPts_, dLongPts_,
-                         dHllInv_, dTemp_, w, stride);
+      launchN(kFusedLongW<T, PD>, nLongPts_, nLongPts_, dLongPts_, dHllInv_,
+              dTemp_, w, stride);
   }
   // Finish the flagged windows of a single-pass apply on the global output.
   void finishLongRuns(T* out) {
@@ -1199,11 +1043,10 @@ class GpuEngine final : public Engine<T> {
     dispatchMode([&](auto impTag, auto infoTag) {
       constexpr bool IM = decltype(impTag)::value;
       constexpr bool HI = decltype(infoTag)::value;
-      hipLaunchKernelGGL((kFusedLongScatter<T, CD, PD, RD, IM, HI>),
-                         dim3(windowGrid(nFlagWins_)), dim3(256), 0, stream_,
-                         nFlagWins_, dFlagWins_, dWinLo_, dWinHi_, nL_,
-                         dCamOf_, dPtOf_, dHpl_, (const T* const*)dJSlots_,
-                         dInfo_, lossKind_, lossD2_, dXPad_, dW_, out);
+      launch(kFusedLongScatter<T, CD, PD, RD, IM, HI>,
+             windowGrid(nFlagWins_), 256, 0, nFlagWins_, dFlagWins_, dWinLo_,
+             dWinHi_, nL_, dCamOf_, dPtOf_, dHpl_, (const T* const*)dJSlots_,
+             dInfo_, lossKind_, lossD2_, dXPad_, dW_, out);
     });
   }
   // Eligibility of the LDS single-pass apply: the camera vector must fit
@@ -1230,7 +1073,7 @@ class GpuEngine final : public Engine<T> {
     int64_t limit = lim > optin ? lim : optin;
     if (knobs_.schurLdsMaxBytes && *knobs_.schurLdsMaxBytes < limit)
       limit = *knobs_.schurLdsMaxBytes;
-    const int64_t need = nc_ * (int64_t)sizeof(T);
+    const int64_t need = (int64_t)ldsBytes();
     if (cus < 1 || need > limit) return;
     if (hipFuncSetAttribute(schurLdsKernel(),
                             hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1265,16 +1108,13 @@ class GpuEngine final : public Engine<T> {
       // the row table's pad columns are zeroed here and never written again
       dCamRow_ = dalloc<T>((int64_t)ncam_ * RcRow<T>::LEN);
       dPtAcc_ = dalloc<T>((int64_t)npt_ * 4);
-      HIP_CHECK(hipMemsetAsync(dCamRow_, 0,
-                               (int64_t)ncam_ * RcRow<T>::LEN * sizeof(T),
-                               stream_));
-      HIP_CHECK(hipMemsetAsync(dPtAcc_, 0, (int64_t)npt_ * 4 * sizeof(T),
-                               stream_));
+      zero(dCamRow_, (int64_t)ncam_ * RcRow<T>::LEN);
+      zero(dPtAcc_, (int64_t)npt_ * 4);
       rcEligible_ = true;
       // Staged gather: the per-wave tiles must fit behind the accumulators
       // (MEGBA_NO_RC_STAGE takes it out); otherwise the per-lane instance
       // runs and nothing else changes.
-      const int64_t stagedNeed = (int64_t)rcLdsBytes(true);
+      const int64_t stagedNeed = (int64_t)ldsBytes(true);
       if (!knobs_.noRcStage && stagedNeed <= limit) {
         if (hipFuncSetAttribute(schurLdsRcKernel(true),
                                 hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1290,46 +1130,41 @@ class GpuEngine final : public Engine<T> {
   // with a per-workgroup LDS accumulator; out is fully overwritten.  With
   // bApplyDot the row reduce carries on to out = HppD x - out and the x.out
   // partials (dPartQ_), which needs nLongPts_ == 0.
-  // With recompute the window kernel is kSchurFusedLdsRc, which rebuilds the
-  // implicit edge from the accepted snapshot instead of reading dJPk_.
-  void schurFusedLdsEcE(XIn x, T* out, bool bApplyDot = false,
-                        bool recompute = false) {
-    windowPrologue(x, recompute ? SchurPath::LdsRecompute : SchurPath::Lds);
-    const size_t ldsBytes = (size_t)nc_ * sizeof(T);
-    if (recompute)
+  // path is Lds or LdsRecompute; for the latter the window kernel is
+  // kSchurFusedLdsRc, which rebuilds the implicit edge from the accepted
+  // snapshot instead of reading dJPk_.
+  void schurFusedLdsEcE(XIn x, T* out, SchurPath path,
+                        bool bApplyDot = false) {
+    windowPrologue(x, path);
+    if (path == SchurPath::LdsRecompute)
       launchSchurLdsRc();
     else
       dispatchMode([&](auto impTag, auto infoTag) {
         constexpr bool IM = decltype(impTag)::value;
         constexpr bool HI = decltype(infoTag)::value;
-        hipLaunchKernelGGL((kSchurFusedLds<T, CD, PD, RD, IM, HI>),
-                           dim3(numCU_), dim3(ldsThreads_), ldsBytes, stream_,
-                           nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
-                           dPtOf_, dHpl_, dJPk_, (const T* const*)dJSlots_,
-                           dInfo_, lossKind_, lossD2_, dXPad_, dHllInv_,
-                           dTemp_, (int)nc_, dLdsRows_);
+        launch(kSchurFusedLds<T, CD, PD, RD, IM, HI>, numCU_, ldsThreads_,
+               ldsBytes(), nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
+               dPtOf_, dHpl_, dJPk_, (const T* const*)dJSlots_, dInfo_,
+               lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_, (int)nc_,
+               dLdsRows_);
       });
     if (bApplyDot) {
-      hipLaunchKernelGGL((kLdsReduceBApplyDot<T, CD>), dim3(ldsReduceGrid()),
-                         dim3(64 * kLdsRedWaves), 0, stream_, numCU_, (int)nc_,
-                         dLdsRows_, dHppD_, x.v, out, dPartQ_);
+      launch(kLdsReduceBApplyDot<T, CD>, ldsReduceGrid(), 64 * kLdsRedWaves, 0,
+             numCU_, (int)nc_, dLdsRows_, dHppD_, x.v, out, dPartQ_);
       return;
     }
-    hipLaunchKernelGGL(kLdsRowsReduce<T>, dim3(ldsReduceGrid()),
-                       dim3(64 * kLdsRedWaves), 0, stream_, numCU_, (int)nc_,
-                       dLdsRows_, out);
+    launch(kLdsRowsReduce<T>, ldsReduceGrid(), 64 * kLdsRedWaves, 0, numCU_,
+           (int)nc_, dLdsRows_, out);
     finishLongRuns(out);
   }
 
-  // local (collective-free) E Cinv E^T x into out on the given path: one of
-  // the tuner's four candidates (schurApply launches OnePass itself)
+  // local (collective-free) E Cinv E^T x into out on the given path; the
+  // tuner passes its four candidates, never OnePass
   void localSchurEcE(SchurPath path, XIn x, T* out) {
     switch (path) {
       case SchurPath::Lds:
-        schurFusedLdsEcE(x, out);
-        break;
       case SchurPath::LdsRecompute:
-        schurFusedLdsEcE(x, out, false, /*recompute=*/true);
+        schurFusedLdsEcE(x, out, path);
         break;
       case SchurPath::FusedEtx:
         etxCinv(x);
@@ -1340,27 +1175,23 @@ class GpuEngine final : public Engine<T> {
         cinvThenEx(dTemp_, out);
         break;
       case SchurPath::OnePass:
-        MEGBA_CHECK(false, "OnePass is not a tuning candidate");
+        schurFusedEcE(x, out);
+        break;
     }
   }
 
   // w = Cinv in, then out += E w.  w is stored 4-padded so the E-side
   // gather is a single aligned vector load per edge (both modes).
   void cinvThenEx(const T* in, T* out) {
-    hipLaunchKernelGGL((kCinvPad<T, PD>), dim3(gridFor(npL_)), dim3(kBlk),
-                       0, stream_, npL_, dHllInv_ + (int64_t)ptLo_ * PP,
-                       in + (int64_t)ptLo_ * PD,
-                       dWPad_ + (int64_t)ptLo_ * 4);
+    launchN(kCinvPad<T, PD>, npL_, npL_, shard(dHllInv_, PP), shard(in, PD),
+            shard(dWPad_, 4));
     spmvEx(dWPad_, out);
   }
   void spmvEtx(XIn x, T* out) {
-    hipLaunchKernelGGL(kZeroRange<T>, dim3(gridFor((int64_t)npL_ * PD)),
-                       dim3(kBlk), 0, stream_, out + (int64_t)ptLo_ * PD,
-                       (int64_t)npL_ * PD);
+    zeroShard(out);
     if (!implicit_) {
-      hipLaunchKernelGGL((kSpmvEtx<T, CD, PD, RD>), dim3(gridFor(nL_)),
-                         dim3(kBlk), 0, stream_, nL_, dCamOf_, dPtOf_, dHpl_,
-                         x.v, out);
+      launchN(kSpmvEtx<T, CD, PD, RD>, nL_, nL_, dCamOf_, dPtOf_, dHpl_, x.v,
+              out);
       return;
     }
     // 16B-aligned padded copy of x: the per-edge camera gather becomes
@@ -1371,48 +1202,38 @@ class GpuEngine final : public Engine<T> {
       const auto kernel = knobs_.etxAtomic
                               ? kSpmvEtxPkAtomic<T, CD, PD, RD, HI>
                               : kSpmvEtxPk<T, CD, PD, RD, HI>;
-      hipLaunchKernelGGL(kernel, dim3(gridFor(nL_)), dim3(kBlk), 0, stream_,
-                         nL_, dCamOf_, dPtOf_, dJPk_,
-                         (const T* const*)dJSlots_, dInfo_, lossKind_,
-                         lossD2_, dXPad_, out);
+      launchN(kernel, nL_, nL_, dCamOf_, dPtOf_, dJPk_,
+              (const T* const*)dJSlots_, dInfo_, lossKind_, lossD2_, dXPad_,
+              out);
     });
   }
   void spmvEx(const T* wv, T* out) {
-    HIP_CHECK(hipMemsetAsync(out, 0, nc_ * sizeof(T), stream_));
+    zero(out, nc_);
     if (implicit_) {
       if (nChunks_ == 0) return;
-      hipLaunchKernelGGL((kSpmvExPk<T, CD, PD, RD>), dim3(nChunks_),
-                         dim3(64), 0, stream_, nChunks_, dChCam_, dChLo_,
-                         dChHi_, dPtOfCam_, dJCamPk_, nL_, wv, out);
+      launch(kSpmvExPk<T, CD, PD, RD>, nChunks_, 64, 0, nChunks_, dChCam_,
+             dChLo_, dChHi_, dPtOfCam_, dJCamPk_, nL_, wv, out);
       return;
     }
     if (nChunks_ > 0)
-      hipLaunchKernelGGL((kSpmvEx<T, CD, PD>), dim3(nChunks_), dim3(64), 0,
-                         stream_, nChunks_, dChCam_, dChLo_, dChHi_,
-                         dPtOfCam_, dHplCam_, nL_, wv, out);
+      launch(kSpmvEx<T, CD, PD>, nChunks_, 64, 0, nChunks_, dChCam_, dChLo_,
+             dChHi_, dPtOfCam_, dHplCam_, nL_, wv, out);
   }
-  // One full PCG iteration (captured as a hipGraph when possible).
-  // vs round 1: the p^T q dot partial is fused into the B-apply, the
-  // two-deep x backup rotation is fused into kUpdateXR, and the standalone
-  // kRedPartial pass + dXBakPrev memcpy are gone (~2 launches + one full
-  // read pass over p,q per iteration — part of the N=8 constant term,
-  // PLAN_r02 item 3).
+  // One full PCG iteration (captured as a hipGraph when possible): the
+  // rotated body, or the seven-kernel one below (docs/INTERNALS.md section 6).
   void pcgBody() {
     if (plan_->rotatedBody) {
       pcgBodyRotated();
       return;
     }
     const int rhoGrid = gridFor(nc_) < kRedBlocks ? gridFor(nc_) : kRedBlocks;
-    hipLaunchKernelGGL((kPrecondRho<T, CD>), dim3(rhoGrid), dim3(kBlk), 0,
-                       stream_, ncam_, dHppInv_, dRr_, dZ_, dPart_);
-    hipLaunchKernelGGL(kXpbySBeta<T>, dim3(gridFor(nc_)), dim3(kBlk), 0,
-                       stream_, nc_, dZ_, dPart_, rhoGrid, slotRhoPrev(),
-                       slotRho(), dP_);
+    launch(kPrecondRho<T, CD>, rhoGrid, kBlk, 0, ncam_, dHppInv_, dRr_, dZ_,
+           dPart_);
+    launchN(kXpbySBeta<T>, nc_, nc_, dZ_, dPart_, rhoGrid, slotRhoPrev(),
+            slotRho(), dP_);
     const int nPartQ = schurApply({dP_, false}, dQ_, /*withDot=*/true);
-    hipLaunchKernelGGL(kUpdateXRAlpha<T>, dim3(gridFor(nc_)), dim3(kBlk), 0,
-                       stream_, nc_, dPart_, rhoGrid, dPartQ_, nPartQ,
-                       slotRhoPrev(), dP_, dQ_, dDeltaX_, dXBak_, dXBakPrev_,
-                       dRr_);
+    launchN(kUpdateXRAlpha<T>, nc_, nc_, dPart_, rhoGrid, dPartQ_, nPartQ,
+            slotRhoPrev(), dP_, dQ_, dDeltaX_, dXBak_, dXBakPrev_, dRr_);
   }
 
   // Blocks of kUpdateXRPrecond (kBlk / CD whole cameras each) = number of
@@ -1434,21 +1255,17 @@ class GpuEngine final : public Engine<T> {
     const int nbR = precondGrid();
     if (plan_->productReadsPad) {
       const PadDst d = padDstFor(plan_->path);
-      hipLaunchKernelGGL((kBetaPPad<T, CD>),
-                         dim3(gridFor((int64_t)ncam_ * PkJ::XP)), dim3(kBlk),
-                         0, stream_, ncam_, dZ_, dPart_, nbR, slotRhoPrev(),
-                         slotRho(), dP_, d.p, d.stride, d.off);
+      launchN(kBetaPPad<T, CD>, (int64_t)ncam_ * PkJ::XP, ncam_, dZ_, dPart_,
+              nbR, slotRhoPrev(), slotRho(), dP_, d.p, d.stride, d.off);
     } else {
-      hipLaunchKernelGGL(kXpbySBeta<T>, dim3(gridFor(nc_)), dim3(kBlk), 0,
-                         stream_, nc_, dZ_, dPart_, nbR, slotRhoPrev(),
-                         slotRho(), dP_);
+      launchN(kXpbySBeta<T>, nc_, nc_, dZ_, dPart_, nbR, slotRhoPrev(),
+              slotRho(), dP_);
     }
     const int nPartQ =
         schurApply({dP_, plan_->productReadsPad}, dQ_, /*withDot=*/true);
-    hipLaunchKernelGGL((kUpdateXRPrecond<T, CD>), dim3(nbR), dim3(kBlk), 0,
-                       stream_, ncam_, slotRho(), dPartQ_, nPartQ,
-                       slotRhoPrev(), dP_, dQ_, dDeltaX_, dXBak_, dXBakPrev_,
-                       dRr_, dHppInv_, dZ_, dPart_);
+    launch(kUpdateXRPrecond<T, CD>, nbR, kBlk, 0, ncam_, slotRho(), dPartQ_,
+           nPartQ, slotRhoPrev(), dP_, dQ_, dDeltaX_, dXBak_, dXBakPrev_, dRr_,
+           dHppInv_, dZ_, dPart_);
   }
 
   // Capture the PCG body as a hipGraph, once.  The implicit path reads the
@@ -1494,16 +1311,15 @@ class GpuEngine final : public Engine<T> {
   // out = E Cinv E^T x in one fused pass (see kSchurFused; measured
   // negative, kept env-gated).
   void schurFusedEcE(XIn x, T* out) {
-    HIP_CHECK(hipMemsetAsync(out, 0, nc_ * sizeof(T), stream_));
+    zero(out, nc_);
     windowPrologue(x, SchurPath::OnePass);
     dispatchMode([&](auto impTag, auto infoTag) {
       constexpr bool IM = decltype(impTag)::value;
       constexpr bool HI = decltype(infoTag)::value;
-      hipLaunchKernelGGL((kSchurFused<T, CD, PD, RD, IM, HI>),
-                         dim3(windowGrid(nWin_)), dim3(256), 0, stream_,
-                         nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
-                         dPtOf_, dHpl_, (const T* const*)dJSlots_, dInfo_,
-                         lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_, out);
+      launch(kSchurFused<T, CD, PD, RD, IM, HI>, windowGrid(nWin_), 256, 0,
+             nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_, dPtOf_, dHpl_,
+             (const T* const*)dJSlots_, dInfo_, lossKind_, lossD2_, dXPad_,
+             dHllInv_, dTemp_, out);
     });
     finishLongRuns(out);
   }
@@ -1515,12 +1331,10 @@ class GpuEngine final : public Engine<T> {
     dispatchMode([&](auto impTag, auto infoTag) {
       constexpr bool IM = decltype(impTag)::value;
       constexpr bool HI = decltype(infoTag)::value;
-      hipLaunchKernelGGL((kEtxCinvFused<T, CD, PD, RD, IM, HI>),
-                         dim3(windowGrid(nWin_)), dim3(256), 0, stream_,
-                         nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_,
-                         dPtOf_, dHpl_, (const T* const*)dJSlots_, dInfo_,
-                         lossKind_, lossD2_, dXPad_, dHllInv_, dTemp_,
-                         dWPad_);
+      launch(kEtxCinvFused<T, CD, PD, RD, IM, HI>, windowGrid(nWin_), 256, 0,
+             nWin_, dWinLo_, dWinHi_, dWinFlag_, nL_, dCamOf_, dPtOf_, dHpl_,
+             (const T* const*)dJSlots_, dInfo_, lossKind_, lossD2_, dXPad_,
+             dHllInv_, dTemp_, dWPad_);
     });
     longRunW(dWPad_, 4);
   }
@@ -1531,19 +1345,14 @@ class GpuEngine final : public Engine<T> {
   // returns how many partials it wrote to dPartQ_ (0 without withDot).
   int schurApply(XIn x, T* q, bool withDot) {
     if (withDot && plan_->mergeReduceBApply) {
-      schurFusedLdsEcE(x, q, /*bApplyDot=*/true,
-                       plan_->path == SchurPath::LdsRecompute);
+      schurFusedLdsEcE(x, q, plan_->path, /*bApplyDot=*/true);
       return ldsReduceGrid();
     }
-    if (plan_->path == SchurPath::OnePass)
-      schurFusedEcE(x, q);
-    else
-      localSchurEcE(plan_->path, x, q);
+    localSchurEcE(plan_->path, x, q);
     allreduce(q, nc_, ncclSum);
     if (withDot) {
-      hipLaunchKernelGGL((kBApplyDot<T, CD>), dim3(bApplyDotGrid()),
-                         dim3(kBlk), 0, stream_, ncam_, dHppD_, x.v, q,
-                         dPartQ_);
+      launch(kBApplyDot<T, CD>, bApplyDotGrid(), kBlk, 0, ncam_, dHppD_, x.v,
+             q, dPartQ_);
       return bApplyDotGrid();
     }
     blockMatVec<CD, 1>(ncam_, dHppD_, x.v, q);

@@ -26,11 +26,19 @@ TABLE = [
       "MEGBA_SCHUR_LDS_MAX_BYTES": str(LDS_NEED - 1)}, "fused-etx"),
     ({"MEGBA_FUSED": "1"}, "fused-etx"),
     ({"MEGBA_NO_PCG_FUSE": "1", "MEGBA_SCHUR_LDS": "1"}, "lds"),
+    ({"MEGBA_SCHUR_RECOMPUTE": "1"}, "lds-recompute"),
+    ({"MEGBA_SCHUR_RECOMPUTE": "1", "MEGBA_NO_SCHUR_RECOMPUTE": "1"},
+     "fused-etx"),
+    ({"MEGBA_SCHUR_RECOMPUTE": "1", "MEGBA_SCHUR_LDS": "1"}, "lds-recompute"),
+    ({"MEGBA_SCHUR_RECOMPUTE": "1", "MEGBA_SCHUR_LDS": "1",
+      "MEGBA_NO_SCHUR_RECOMPUTE": "1"}, "lds"),
+    ({"MEGBA_SCHUR_RECOMPUTE": "1", "MEGBA_NO_SCHUR_LDS": "1"}, "fused-etx"),
 ]
 
 PATH_KNOBS = ["MEGBA_SCHUR_LDS", "MEGBA_NO_SCHUR_LDS", "MEGBA_NO_ETXFUSE",
               "MEGBA_ETXFUSE", "MEGBA_SCHUR_LDS_MAX_BYTES", "MEGBA_FUSED",
-              "MEGBA_NO_PCG_FUSE", "MEGBA_TUNE_VERBOSE"]
+              "MEGBA_NO_PCG_FUSE", "MEGBA_SCHUR_RECOMPUTE",
+              "MEGBA_NO_SCHUR_RECOMPUTE", "MEGBA_TUNE_VERBOSE"]
 
 
 @pytest.fixture(scope="module")
