@@ -82,7 +82,8 @@ def pybind_flags():
     return out
 
 
-EXAMPLES = ["bal_solve_cpp", "bal_custom_edge_cpp", "bal_priors_cpp"]
+EXAMPLES = ["bal_solve_cpp", "bal_custom_edge_cpp", "bal_priors_cpp",
+            "bal_covariance_cpp"]
 
 
 def build_examples(objs, force=False):

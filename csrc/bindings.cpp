@@ -12,6 +12,7 @@
 
 #include "megba/bal_functor.hpp"
 #include "megba/common.hpp"
+#include "megba/covariance.hpp"
 #include "megba/custom.hpp"
 #include "megba/jv/jetvector.hpp"
 #include "megba/cpu_engine.hpp"
@@ -331,13 +332,43 @@ struct PyProblem {
   void processDiag(double region) {
     withEngine([&](auto& e) { e.processDiag(region); return 0; });
   }
-  int solveLinear(int maxIter, double tol, double refuseRatio) {
+  int solveLinear(int maxIter, double tol, double refuseRatio, double relTol) {
     SolverOptionPCG s;
     s.maxIter = maxIter;
     s.tol = tol;
     s.refuseRatio = refuseRatio;
+    s.relTol = relTol;
     py::gil_scoped_release rel;
     return withEngine([&](auto& e) { return e.solveLinear(s); });
+  }
+
+  // Marginal covariance of the given vertices (covariance.hpp).
+  py::dict covariance(const std::vector<int>& camIds,
+                      const std::vector<int>& ptIds, double tol, int maxIter,
+                      bool strict) {
+    MEGBA_CHECK(engD || engF, "call build() first");
+    // H's condition number is about 5e11 already on a 12-camera problem
+    MEGBA_CHECK(isDouble, "covariance needs dtype float64");
+    CovarianceOption o;
+    o.tol = tol;
+    o.maxIter = maxIter;
+    o.strict = strict;
+    CovarianceResult r;
+    {
+      py::gil_scoped_release rel;
+      r = computeCovariance(*engD, camIds, ptIds, o);
+    }
+    py::dict d;
+    py::array_t<double> joint({r.n, r.n});
+    std::copy(r.joint.begin(), r.joint.end(), joint.mutable_data());
+    d["joint"] = joint;
+    d["iters"] = py::array_t<int>((py::ssize_t)r.iters.size(), r.iters.data());
+    py::array_t<bool> conv((py::ssize_t)r.converged.size());
+    for (size_t i = 0; i < r.converged.size(); ++i)
+      conv.mutable_data()[i] = r.converged[i] != 0;
+    d["converged"] = conv;
+    d["asymmetry"] = r.asymmetry;
+    return d;
   }
   void updateParams() {
     withEngine([&](auto& e) { e.updateParams(); return 0; });
@@ -515,7 +546,11 @@ PYBIND11_MODULE(_core, m) {
       .def("build_linear_system", &PyProblem::buildLinearSystem)
       .def("process_diag", &PyProblem::processDiag)
       .def("solve_linear", &PyProblem::solveLinear, py::arg("max_iter") = 100,
-           py::arg("tol") = 1e-1, py::arg("refuse_ratio") = 1.0)
+           py::arg("tol") = 1e-1, py::arg("refuse_ratio") = 1.0,
+           py::arg("rel_tol") = 0.0)
+      .def("covariance", &PyProblem::covariance, py::arg("cam_idx"),
+           py::arg("pt_idx"), py::arg("tol") = 1e-10,
+           py::arg("max_iter") = 2000, py::arg("strict") = true)
       .def("update_params", &PyProblem::updateParams)
       .def("rho_denominator", &PyProblem::rhoDenominator)
       .def("delta_x_l2", &PyProblem::deltaXL2)

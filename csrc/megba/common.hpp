@@ -26,6 +26,13 @@ struct SolverOptionPCG {
   int maxIter = 100;
   double tol = 1e-1;          // absolute threshold on |r^T z| (reference semantics)
   double refuseRatio = 1.0;   // early stop: rho > refuseRatio * rhoMin -> restore backup
+  // Relative stop, off at 0: also end once |rho_k| < relTol * |rho_0|, rho_0
+  // the first rho the loop reads.  A unit right-hand side has a tiny rho_0, so
+  // the absolute tol cannot judge it (covariance.hpp).
+  double relTol = 0.0;
+  // Raise instead of retrying a failed block inversion with a jitter on the
+  // diagonal: a regularised block gives a meaningless covariance.
+  bool refuseJitter = false;
 };
 
 struct AlgoOptionLM {

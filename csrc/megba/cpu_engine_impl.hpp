@@ -336,7 +336,7 @@ class CpuEngine final : public Engine<T> {
   }
 
   int solveLinear(const SolverOptionPCG& opt) override {
-    invertBlocks();
+    invertBlocks(opt.refuseJitter);
     const int64_t nc = (int64_t)ncam_ * CD;
     const T* gc = g_.data();
     const T* gp = g_.data() + nc;
@@ -356,8 +356,9 @@ class CpuEngine final : public Engine<T> {
 
     int n = 0;
     T rho = T(0), rhoPrev = T(0);
-    double rhoMin = INFINITY;
+    double rhoMin = INFINITY, rho0 = 0.0;
     bool done = false;
+    relStopHit_ = false;
     while (!done && n < opt.maxIter) {
       applyHppInv(r.data(), z.data());
       rho = dotFull(r.data(), z.data(), nc);
@@ -381,8 +382,11 @@ class CpuEngine final : public Engine<T> {
         r[i] -= alpha * q[i];
       }
       rhoPrev = rho;
+      if (n == 0) rho0 = std::abs((double)rho);
       ++n;
       done = std::abs((double)rho) < opt.tol;
+      if (opt.relTol > 0.0 && std::abs((double)rho) < opt.relTol * rho0)
+        done = relStopHit_ = true;
     }
     // Back-substitution: deltaX_p = Cinv * (g_p - E^T x).
     spmvEtx(x.data(), temp.data());
@@ -473,6 +477,45 @@ class CpuEngine final : public Engine<T> {
     }
     for (size_t i = 0; i < pts_.size(); ++i) pts[i] = (double)pts_[i];
   }
+  // ---- other right-hand sides (covariance.hpp) -----------------------------
+  EngineShape shape() const override { return {ncam_, npt_, CD, PD}; }
+  bool isFixed(bool camera, int id) const override {
+    return (camera ? camFixed_[id] : ptFixed_[id]) != 0;
+  }
+  void setUnitRhs(int64_t row) override {
+    MEGBA_CHECK(row >= 0 && row < dim_, "unit right-hand side out of range");
+    std::fill(g_.begin(), g_.end(), T(0));
+    std::fill(deltaX_.begin(), deltaX_.end(), T(0));
+    if (ownsRow(row)) g_[row] = T(1);
+  }
+  void readDeltaXRows(const int64_t* rows, int n, double* out) override {
+    const int64_t nc = (int64_t)ncam_ * CD;
+    // a replicated camera row counts once in the sum: rank 0 supplies it
+    for (int i = 0; i < n; ++i) {
+      MEGBA_CHECK(rows[i] >= 0 && rows[i] < dim_, "deltaX row out of range");
+      const bool mine = rows[i] < nc ? rank_ == 0 : ownsRow(rows[i]);
+      out[i] = mine ? (double)deltaX_[rows[i]] : 0.0;
+    }
+    if (world_ == 1 || n == 0) return;
+    if (arD_) {
+      arD_(out, (size_t)n, 's');
+    } else if (ar_) {
+      std::vector<T> t(out, out + n);
+      ar_(t.data(), (size_t)n, 's');
+      for (int i = 0; i < n; ++i) out[i] = (double)t[i];
+    }
+  }
+  void saveLinearState() override {
+    gSaved_ = g_;
+    deltaXSaved_ = deltaX_;
+  }
+  void restoreLinearState() override {
+    MEGBA_CHECK(gSaved_.size() == g_.size(), "no saved linear state");
+    g_ = gSaved_;
+    deltaX_ = deltaXSaved_;
+  }
+  bool relStopHit() const override { return relStopHit_; }
+
   DenseDump dump() const override {
     DenseDump d;
     d.e0 = e0_;
@@ -702,17 +745,41 @@ class CpuEngine final : public Engine<T> {
     }
   }
 
-  void invertBlocks() {
-#pragma omp parallel for num_threads(nt_) schedule(static)
+  // Camera rows are replicated, a point row belongs to one rank.
+  bool ownsRow(int64_t row) const {
+    const int64_t nc = (int64_t)ncam_ * CD;
+    return row < nc || (row >= nc + (int64_t)ptLo_ * PD &&
+                        row < nc + (int64_t)ptHi_ * PD);
+  }
+
+  // refuseJitter: a failed plain inversion is an error on every rank instead
+  // of a retry with a regularised block.
+  void invertBlocks(bool refuseJitter) {
+    int failed = 0;
+#pragma omp parallel for num_threads(nt_) schedule(static) \
+    reduction(max : failed)
     for (int c = 0; c < ncam_; ++c) {
-      if (!spdInvert<T, CD>(&HppD_[(size_t)c * CC], &HppInv_[(size_t)c * CC]))
+      if (spdInvert<T, CD>(&HppD_[(size_t)c * CC], &HppInv_[(size_t)c * CC]))
+        continue;
+      failed = 1;
+      if (!refuseJitter)
         jitterInvert<CD>(&HppD_[(size_t)c * CC], &HppInv_[(size_t)c * CC]);
     }
-#pragma omp parallel for num_threads(nt_) schedule(static)
+#pragma omp parallel for num_threads(nt_) schedule(static) \
+    reduction(max : failed)
     for (int p = ptLo_; p < ptHi_; ++p) {
-      if (!spdInvert<T, PD>(&HllD_[(size_t)p * PP], &HllInv_[(size_t)p * PP]))
+      if (spdInvert<T, PD>(&HllD_[(size_t)p * PP], &HllInv_[(size_t)p * PP]))
+        continue;
+      failed = 1;
+      if (!refuseJitter)
         jitterInvert<PD>(&HllD_[(size_t)p * PP], &HllInv_[(size_t)p * PP]);
     }
+    if (!refuseJitter) return;
+    // point blocks are rank-local: agree on the outcome before raising
+    if (world_ > 1) failed = scalarAr((double)failed, 'm') > 0.0;
+    MEGBA_CHECK(!failed,
+                "covariance: singular Hessian block (a plain block inversion "
+                "failed and the jitter retry is refused)");
   }
 
   template <int D>
@@ -910,6 +977,8 @@ class CpuEngine final : public Engine<T> {
   std::vector<T> rCur_, JcCur_, JpCur_, rBak_, JcBak_, JpBak_;
   std::vector<T> Hpp_, Hll_, Hpl_, g_, HppD_, HllD_, HppInv_, HllInv_;
   std::vector<T> deltaX_, deltaXBak_, gBak_;
+  std::vector<T> gSaved_, deltaXSaved_;  // saveLinearState
+  bool relStopHit_ = false;
   PriorSet camPr_, ctrPr_, ptPr_;  // camera parameter / centre / point priors
   T priorChi2_ = T(0);             // this rank's prior share of the last forward
   std::vector<T> exScratch_, asmScratch_;  // per-thread reduction buffers

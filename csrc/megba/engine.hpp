@@ -19,6 +19,10 @@ struct DenseDump {
   std::vector<double> g, deltaX;       // camera block first
 };
 
+struct EngineShape {
+  int ncam = 0, npt = 0, camDim = 0, ptDim = 0;
+};
+
 template <typename T>
 class Engine {
  public:
@@ -70,6 +74,29 @@ class Engine {
   // rank must call it (point shards are merged with an allreduce).
   virtual void getParams(double* cams, double* pts) = 0;
   virtual DenseDump dump() const = 0;
+
+  // ---- solves against other right-hand sides (covariance.hpp) -------------
+  // Rows are global indices in the camera-first ordering of g / deltaX:
+  // camDim * cam + i, then camDim * ncam + ptDim * pt + i.
+  virtual EngineShape shape() const = 0;
+  virtual bool isFixed(bool camera, int id) const = 0;
+
+  // g := e_row, deltaX := 0 (solveLinear warm-starts from deltaX).  A camera
+  // row is set on every rank (solveLinear divides g_c by the world size
+  // before its allreduce), a point row on the rank that owns the point.
+  virtual void setUnitRhs(int64_t row) = 0;
+
+  // out[i] = deltaX[rows[i]] in double.  COLLECTIVE when worldSize>1: camera
+  // rows are replicated, point rows come from the rank that owns the point.
+  virtual void readDeltaXRows(const int64_t* rows, int n, double* out) = 0;
+
+  // Save / restore g and deltaX in buffers of their own: backupGDx /
+  // rollbackGDx belong to the LM loop.
+  virtual void saveLinearState() = 0;
+  virtual void restoreLinearState() = 0;
+
+  // Whether the last solveLinear ended on the relTol rule.
+  virtual bool relStopHit() const = 0;
 };
 
 }  // namespace megba

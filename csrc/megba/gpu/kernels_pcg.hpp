@@ -249,6 +249,27 @@ __global__ void kZeroRange(T* p, int64_t n) {
        i += (int64_t)gridDim.x * kBlk)
     p[i] = T(0);
 }
+// v[i] = val: the one nonzero of a unit right-hand side (the host checks i).
+template <typename T>
+__global__ void kSetElement(T* v, int64_t i, T val) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) v[i] = val;
+}
+// out[k] = v[rows[k]] in double for the rows this rank supplies, 0 for the
+// others, so that a sum over the ranks holds every row once: rows below nc
+// (replicated camera rows) where camOwner is set, rows in [ptLo, ptHi) (this
+// rank's point shard) always.  The host checks rows against v's length.
+template <typename T>
+__global__ void kGatherRows(int n, const T* __restrict__ v,
+                            const int64_t* __restrict__ rows, int64_t nc,
+                            int64_t ptLo, int64_t ptHi, bool camOwner,
+                            double* __restrict__ out) {
+  for (int64_t k = blockIdx.x * (int64_t)kBlk + threadIdx.x; k < n;
+       k += (int64_t)gridDim.x * kBlk) {
+    const int64_t row = rows[k];
+    const bool mine = row < nc ? camOwner : (row >= ptLo && row < ptHi);
+    out[k] = mine ? (double)v[row] : 0.0;
+  }
+}
 // deltaX_p = HllInv * (g_p - temp)  (local point shard)
 template <typename T, int PD>
 __global__ void kBackSub(int npt, const T* __restrict__ HllInv,

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "covariance.hpp"
 #include "cpu_engine.hpp"
 #include "custom.hpp"
 #include "lm.hpp"
@@ -179,23 +180,7 @@ class GraphProblem {
   LMReport solve(const ProblemOption& popt, const AlgoOptionLM& algo,
                  const SolverOptionPCG& sopt) {
     BAProblemHost prob = assemble();
-    ProblemOption opt = popt;
-    opt.camDim = prob.camDim;
-    opt.ptDim = prob.ptDim;
-    opt.resDim = prob.resDim;
-    validatePriors(prob, (bool)customForward_);
-    ProblemIndex ix = buildIndex(prob, opt.worldSize);
-    std::unique_ptr<Engine<double>> eng;
-    if (opt.device == Device::CPU) {
-      eng = makeCpuEngine<double>(prob, ix, opt, nullptr, customForward_);
-    } else {
-#ifdef MEGBA_WITH_GPU
-      eng = makeGpuEngine<double>(prob, ix, opt, std::string(),
-                                  customForward_);
-#else
-      MEGBA_CHECK(false, "built without GPU support");
-#endif
-    }
+    std::unique_ptr<Engine<double>> eng = makeEngine(prob, popt);
     LMReport rep = runLM<double>(*eng, algo, sopt);
     const int cd = prob.camDim;
     std::vector<double> camOut(cams_.size() * cd), ptOut(pts_.size() * 3);
@@ -208,7 +193,64 @@ class GraphProblem {
     return rep;
   }
 
+  // Joint marginal covariance of `vertices` (appended vertices, any order,
+  // each once) at their current estimations; rows and columns of the result
+  // follow the order of `vertices`.  Like solve() it builds the problem anew
+  // and keeps no engine; covariance.hpp says what the matrix is.
+  CovarianceResult covariance(const std::vector<BaseVertex*>& vertices,
+                              const ProblemOption& popt,
+                              const CovarianceOption& copt = {}) {
+    std::vector<int> camIds, ptIds;
+    for (const BaseVertex* v : vertices) {
+      MEGBA_CHECK(v != nullptr && v->slot >= 0,
+                  "covariance of a vertex that is not in this problem");
+      const auto& own = v->kind == VertexKind::CAMERA ? cams_ : pts_;
+      MEGBA_CHECK(v->slot < (int)own.size() && own[v->slot] == v,
+                  "covariance of a vertex that is not in this problem");
+      (v->kind == VertexKind::CAMERA ? camIds : ptIds).push_back(v->slot);
+    }
+    BAProblemHost prob = assemble();
+    std::unique_ptr<Engine<double>> eng = makeEngine(prob, popt);
+    const CovarianceResult raw = computeCovariance(*eng, camIds, ptIds, copt);
+    // array order (cameras first) -> the order of `vertices`
+    const int cd = prob.camDim, nc = cd * (int)camIds.size();
+    std::vector<int> at;
+    int ic = 0, ip = 0;
+    for (const BaseVertex* v : vertices) {
+      const bool cam = v->kind == VertexKind::CAMERA;
+      const int first = cam ? cd * ic++ : nc + 3 * ip++;
+      for (int k = 0; k < (cam ? cd : 3); ++k) at.push_back(first + k);
+    }
+    CovarianceResult res = raw;
+    const int n = raw.n;
+    for (int i = 0; i < n; ++i) {
+      res.iters[i] = raw.iters[at[i]];
+      res.converged[i] = raw.converged[at[i]];
+      for (int j = 0; j < n; ++j)
+        res.joint[(size_t)i * n + j] = raw.joint[(size_t)at[i] * n + at[j]];
+    }
+    return res;
+  }
+
  private:
+  std::unique_ptr<Engine<double>> makeEngine(const BAProblemHost& prob,
+                                             const ProblemOption& popt) const {
+    ProblemOption opt = popt;
+    opt.camDim = prob.camDim;
+    opt.ptDim = prob.ptDim;
+    opt.resDim = prob.resDim;
+    validatePriors(prob, (bool)customForward_);
+    ProblemIndex ix = buildIndex(prob, opt.worldSize);
+    if (opt.device == Device::CPU)
+      return makeCpuEngine<double>(prob, ix, opt, nullptr, customForward_);
+#ifdef MEGBA_WITH_GPU
+    return makeGpuEngine<double>(prob, ix, opt, std::string(), customForward_);
+#else
+    MEGBA_CHECK(false, "built without GPU support");
+    return nullptr;
+#endif
+  }
+
   BAProblemHost assemble() const {
     MEGBA_CHECK(!edges_.empty(), "no edges");
     BAProblemHost p;

@@ -228,6 +228,42 @@ class GraphProblem:
             getattr(prob, setter)(idx, mean, pinfo)
         return prob
 
+    def covariance(self, vertices, device="cpu", diff="auto",
+                   schur="explicit", loss="none", loss_delta=1.0,
+                   custom_forward=None, intrinsics=None, tol=1e-10,
+                   max_iter=2000, strict=True):
+        """Joint marginal covariance of `vertices` (appended CameraVertex /
+        PointVertex objects, any order, each once) at their current
+        estimations; rows and columns follow the order of `vertices`.  Like
+        solve() it builds the problem anew and keeps no engine; see
+        BAProblem.covariance for what the matrix is."""
+        cams, pts = [], []
+        for v in vertices:
+            if not isinstance(v, BaseVertex):
+                raise TypeError("covariance expects BaseVertex objects")
+            own = self._cams if v.kind == CAMERA else self._pts
+            if v._slot is None or v._slot >= len(own) or own[v._slot] is not v:
+                raise ValueError("megba: covariance of a vertex that is not "
+                                 "in this problem")
+            (cams if v.kind == CAMERA else pts).append(v._slot)
+        p = self._assemble()
+        p.build(device=device, diff=diff, schur=schur, loss=loss,
+                loss_delta=loss_delta, custom_forward=custom_forward,
+                intrinsics=intrinsics)
+        joint = p.covariance(cams, pts, tol=tol, max_iter=max_iter,
+                             strict=strict)["joint"]
+        # array order (cameras first) -> the order of `vertices`
+        cd = p.cams.shape[1]
+        at, nc, ic, ip = [], cd * len(cams), 0, 0
+        for v in vertices:
+            if v.kind == CAMERA:
+                at += range(cd * ic, cd * (ic + 1))
+                ic += 1
+            else:
+                at += range(nc + 3 * ip, nc + 3 * (ip + 1))
+                ip += 1
+        return joint[np.ix_(at, at)]
+
     def solve(self, device="cpu", dtype="float64", diff="auto",
               schur="explicit", loss="none", loss_delta=1.0,
               custom_forward=None, intrinsics=None, **solve_kw):

@@ -108,6 +108,51 @@ class BAProblem:
             solver_refuse_ratio=solver_refuse_ratio,
             force_iterations=force_iterations, verbose=verbose)
 
+    # -- marginal covariances ------------------------------------------------
+    def covariance(self, cam_idx=None, pt_idx=None, tol=1e-10, max_iter=2000,
+                   strict=True):
+        """Marginal covariance of the given cameras and points at the current
+        parameters: the matching sub-matrix of H^-1, H = J^T W J plus the
+        prior terms (the Hessian the LM step uses, robust-loss weights and
+        information matrices included).  It is the covariance under
+        unit-variance weighted residuals; multiply by a variance factor
+        chi^2 / dof yourself if you want one.
+
+        Call it after build(), usually after solve().  float64 only.  The
+        gauge must be fixed by priors or fixed vertices, otherwise H is
+        singular and the solves do not converge.  One unit-right-hand-side
+        Schur PCG solve per row of every requested block (9 per BAL camera,
+        3 per point); tol is the relative residual each solve reaches.
+        Fixed vertices get zero rows and columns.
+
+        Returns a dict: "joint" (n, n) with n = camDim*len(cam_idx) +
+        3*len(pt_idx), cameras first in the order given; "cam_cov"
+        (m, camDim, camDim) and "pt_cov" (k, 3, 3), its diagonal blocks;
+        "iters" and "converged" per column; "asymmetry",
+        max|A - A^T| / max|A| of the raw columns before symmetrising, a free
+        accuracy indicator.  strict=True raises if a column did not
+        converge, strict=False returns with the flags set.
+
+        COLLECTIVE when world_size>1: every rank calls it with the same
+        arguments and gets the same result.  An LM session in progress
+        (lm_init / lm_step) continues unchanged afterwards."""
+        if not self._built:
+            raise RuntimeError("megba: call build() first")
+        cams = [] if cam_idx is None else [int(i) for i in cam_idx]
+        pts = [] if pt_idx is None else [int(i) for i in pt_idx]
+        out = self._core.covariance(cams, pts, tol=tol, max_iter=max_iter,
+                                    strict=strict)
+        joint = out["joint"]
+        cd = self.cams.shape[1]
+        nc = cd * len(cams)
+        out["cam_cov"] = np.array(
+            [joint[cd * i:cd * (i + 1), cd * i:cd * (i + 1)]
+             for i in range(len(cams))]).reshape(len(cams), cd, cd)
+        out["pt_cov"] = np.array(
+            [joint[nc + 3 * i:nc + 3 * (i + 1), nc + 3 * i:nc + 3 * (i + 1)]
+             for i in range(len(pts))]).reshape(len(pts), 3, 3)
+        return out
+
     # -- low-level steps (tests) -------------------------------------------
     def __getattr__(self, name):
         # Delegate fine-grained methods to the core object.

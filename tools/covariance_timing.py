@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""What a marginal covariance costs on the GPU.
+
+Builds the bench's Venice-shaped synthetic problem (fp64, implicit Schur)
+with a centre prior on every camera (the datum), takes a few LM steps, then
+asks for the covariance of one camera and of one point (9 and 3 unit
+right-hand side Schur PCG solves) at each --tol.  Prints the PCG iterations
+of every column, the milliseconds per vertex block and per PCG iteration
+(device synchronised before each clock read) and one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import megba_amd as mb  # noqa: E402
+from prior_overhead import centres  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="venice1778")
+    ap.add_argument("--lm-steps", type=int, default=3)
+    ap.add_argument("--camera", type=int, default=0)
+    ap.add_argument("--point", type=int, default=0)
+    ap.add_argument("--tol", type=float, nargs="+",
+                    default=[1e-10, 1e-8, 1e-6, 1e-4])
+    ap.add_argument("--max-iter", type=int, default=2000)
+    args = ap.parse_args()
+    from bench import MODELS
+    from megba_amd import _core
+    shape = MODELS[args.model]
+    cams, pts, ci, pi, meas = mb.synthesize_bal(shape["ncam"], shape["npt"],
+                                                shape["nobs"], seed=7)
+    rng = np.random.default_rng(1)
+    p = mb.BAProblem(cams, pts, ci, pi, meas)
+    p.set_camera_center_prior(
+        np.arange(len(cams)),
+        centres(cams) + rng.normal(0, 0.05, (len(cams), 3)),
+        np.tile(mb.pack_sym(1e4 * np.eye(3)), (len(cams), 1)))
+    p.build(device="gpu", dtype="float64", schur="implicit")
+    p.lm_init(tau=1e4, solver_max_iter=100, solver_tol=0.0,
+              solver_refuse_ratio=1e30, force_iterations=True, verbose=False)
+    for _ in range(args.lm_steps):
+        log = p.lm_step()
+    print(f"{args.model}: {len(cams)} cams, {len(pts)} pts, {len(ci)} obs; "
+          f"chi2 {log['chi2']:.6g} after {args.lm_steps} LM steps", flush=True)
+
+    def timed(cam_idx, pt_idx, tol):
+        _core.device_synchronize()
+        t0 = time.perf_counter()
+        cov = p.covariance(cam_idx=cam_idx, pt_idx=pt_idx, tol=tol,
+                           max_iter=args.max_iter, strict=False)
+        _core.device_synchronize()
+        return cov, (time.perf_counter() - t0) * 1000
+
+    # the first call pays the Schur path choice of the engine's first solve
+    timed([args.camera], [args.point], args.tol[0])
+    out = dict(model=args.model, max_iter=args.max_iter, results=[])
+    for tol in args.tol:
+        print(f"tol {tol:g} (PCG stops on rho/rho_0 < {tol * tol:g}, or "
+              f"after {args.max_iter} iterations)")
+        std = []
+        for name, cams_, pts_ in (("camera", [args.camera], []),
+                                  ("point", [], [args.point])):
+            cov, ms = timed(cams_, pts_, tol)
+            its = [int(i) for i in cov["iters"]]
+            print(f"  {name:6s} iters/column {its}  converged "
+                  f"{int(cov['converged'].sum())}/{len(its)}  asymmetry "
+                  f"{cov['asymmetry']:.3g}")
+            print(f"  {'':6s} {ms:9.1f} ms per block (relinearisation "
+                  f"included), {ms / sum(its):6.3f} ms per PCG iteration",
+                  flush=True)
+            std.append(np.sqrt(np.diag(cov["joint"])))
+            out["results"].append(dict(
+                tol=tol, block=name, iters=its, ms=ms,
+                converged=[bool(c) for c in cov["converged"]],
+                asymmetry=float(cov["asymmetry"])))
+        print("  camera std (aa, t, f, k1, k2):",
+              np.array2string(std[0], precision=4))
+        print("  point std:", np.array2string(std[1], precision=4))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
