@@ -345,7 +345,7 @@ struct PyProblem {
   // Marginal covariance of the given vertices (covariance.hpp).
   py::dict covariance(const std::vector<int>& camIds,
                       const std::vector<int>& ptIds, double tol, int maxIter,
-                      bool strict) {
+                      bool strict, int batch) {
     MEGBA_CHECK(engD || engF, "call build() first");
     // H's condition number is about 5e11 already on a 12-camera problem
     MEGBA_CHECK(isDouble, "covariance needs dtype float64");
@@ -353,6 +353,7 @@ struct PyProblem {
     o.tol = tol;
     o.maxIter = maxIter;
     o.strict = strict;
+    o.batch = batch;
     CovarianceResult r;
     {
       py::gil_scoped_release rel;
@@ -368,7 +369,31 @@ struct PyProblem {
       conv.mutable_data()[i] = r.converged[i] != 0;
     d["converged"] = conv;
     d["asymmetry"] = r.asymmetry;
+    d["products"] = r.products;
     return d;
+  }
+  // Most columns a batched covariance solve carries at once (1: column loop).
+  int maxBatch() {
+    MEGBA_CHECK(engD || engF, "call build() first");
+    return isDouble ? engD->maxBatch() : engF->maxBatch();
+  }
+  // S X for the columns of X (Engine::schurApplyColumns, a test hook).
+  py::array_t<double> schurApply(
+      py::array_t<double, py::array::c_style | py::array::forcecast> X,
+      bool batched) {
+    MEGBA_CHECK(engD, "schur_apply needs a built float64 problem");
+    const EngineShape sh = engD->shape();
+    MEGBA_CHECK(X.ndim() == 2 &&
+                    X.shape(0) == (py::ssize_t)sh.ncam * sh.camDim &&
+                    X.shape(1) >= 1,
+                "schur_apply: X must be (camDim * ncam, k)");
+    const int k = (int)X.shape(1);
+    py::array_t<double> out({X.shape(0), X.shape(1)});
+    {
+      py::gil_scoped_release rel;
+      engD->schurApplyColumns(X.data(), k, batched, out.mutable_data());
+    }
+    return out;
   }
   void updateParams() {
     withEngine([&](auto& e) { e.updateParams(); return 0; });
@@ -550,7 +575,11 @@ PYBIND11_MODULE(_core, m) {
            py::arg("rel_tol") = 0.0)
       .def("covariance", &PyProblem::covariance, py::arg("cam_idx"),
            py::arg("pt_idx"), py::arg("tol") = 1e-10,
-           py::arg("max_iter") = 2000, py::arg("strict") = true)
+           py::arg("max_iter") = 2000, py::arg("strict") = true,
+           py::arg("batch") = 1)
+      .def("max_batch", &PyProblem::maxBatch)
+      .def("schur_apply", &PyProblem::schurApply, py::arg("X"),
+           py::arg("batched") = true)
       .def("update_params", &PyProblem::updateParams)
       .def("rho_denominator", &PyProblem::rhoDenominator)
       .def("delta_x_l2", &PyProblem::deltaXL2)

@@ -8,7 +8,9 @@
 // g = e_j and no damping dx is column j of H^-1, and its entries at the
 // requested vertices are the wanted covariance and cross-covariance entries.
 // One vertex block of dimension D costs D solves; no dense S is formed and
-// every tuned product path carries the solves unchanged.
+// every tuned product path carries the solves unchanged.  With batch > 1 the
+// columns of a block are solved together where the engine has a batched
+// product (Engine::solveUnitBatch): they share every pass over J.
 //
 // The result is the covariance under unit-variance weighted residuals.
 // Scaling by a variance factor chi^2 / dof is left to the caller.
@@ -36,12 +38,21 @@ struct CovarianceResult {
   std::vector<int> iters;      // PCG iterations per column (0: fixed vertex)
   std::vector<uint8_t> converged;  // per column (1 for a fixed vertex)
   double asymmetry = 0.0;      // max|A - A^T| / max|A| before symmetrising
+  // Schur products S p the engine applied during the call (PCG iterations
+  // and initial residuals; a batched application counts once)
+  int64_t products = 0;
 };
 
 struct CovarianceOption {
   double tol = 1e-10;  // relative residual; the PCG stops on rho/rho_0 < tol^2
   int maxIter = 2000;
   bool strict = true;  // raise if a column does not converge
+  // Columns solved together, at most: the non-fixed columns of a vertex block
+  // go to Engine::solveUnitBatch in groups of min(batch, maxBatch()); a
+  // group never spans two vertices.  1 is the column loop.  An engine
+  // without a batched product (the CPU engine: maxBatch() == 1) accepts any
+  // batch and runs the column loop.
+  int batch = 1;
 };
 
 // COLLECTIVE when worldSize>1: every rank calls it with the same arguments
@@ -56,6 +67,7 @@ inline CovarianceResult computeCovariance(Engine<double>& eng,
               "covariance: no vertices requested");
   MEGBA_CHECK(opt.tol > 0.0 && opt.maxIter > 0,
               "covariance: tol and max_iter must be positive");
+  MEGBA_CHECK(opt.batch >= 1, "covariance: batch must be at least 1");
   const auto checkIds = [](const std::vector<int>& ids, int count,
                            const char* what) {
     std::vector<int> sorted(ids);
@@ -111,23 +123,49 @@ inline CovarianceResult computeCovariance(Engine<double>& eng,
   sopt.relTol = opt.tol * opt.tol;
   sopt.refuseJitter = true;
   std::vector<double> col(n);
+  const int64_t productsBefore = eng.productCount();
+  const int width = std::min(opt.batch, eng.maxBatch());
   try {
     // 1 + 1/region is exactly 1: no damping
     eng.processDiag(std::numeric_limits<double>::infinity());
-    for (int j = 0; j < n; ++j) {
-      if (fixedRow[j]) continue;
-      eng.setUnitRhs(rows[j]);
-      res.iters[j] = eng.solveLinear(sopt);
-      res.converged[j] = eng.relStopHit();
-      eng.readDeltaXRows(rows.data(), n, col.data());
-      for (int i = 0; i < n; ++i)
-        res.joint[(size_t)i * n + j] = fixedRow[i] ? 0.0 : col[i];
+    if (width <= 1) {
+      for (int j = 0; j < n; ++j) {
+        if (fixedRow[j]) continue;
+        eng.setUnitRhs(rows[j]);
+        res.iters[j] = eng.solveLinear(sopt);
+        res.converged[j] = eng.relStopHit();
+        eng.readDeltaXRows(rows.data(), n, col.data());
+        for (int i = 0; i < n; ++i)
+          res.joint[(size_t)i * n + j] = fixedRow[i] ? 0.0 : col[i];
+      }
+    } else {
+      // the columns of one vertex block, `width` at a time
+      std::vector<double> cols;
+      std::vector<uint8_t> conv(width);
+      for (int first = 0; first < n;) {
+        const int dim = first < sh.camDim * (int)camIds.size() ? sh.camDim
+                                                               : sh.ptDim;
+        for (int j = first; j < first + dim && !fixedRow[first]; j += width) {
+          const int k = std::min(width, first + dim - j);
+          cols.assign((size_t)n * k, 0.0);
+          eng.solveUnitBatch(rows.data() + j, k, sopt, rows.data(), n,
+                             cols.data(), res.iters.data() + j, conv.data());
+          for (int c = 0; c < k; ++c) {
+            res.converged[j + c] = conv[c];
+            for (int i = 0; i < n; ++i)
+              res.joint[(size_t)i * n + j + c] =
+                  fixedRow[i] ? 0.0 : cols[(size_t)i * k + c];
+          }
+        }
+        first += dim;
+      }
     }
   } catch (...) {
     eng.restoreLinearState();
     throw;
   }
   eng.restoreLinearState();
+  res.products = eng.productCount() - productsBefore;
 
   double maxAbs = 0.0, maxAsym = 0.0;
   for (int i = 0; i < n; ++i)

@@ -919,6 +919,7 @@ class CpuEngine final : public Engine<T> {
 
   // q = S x = HppD x - E Cinv E^T x   (2 allreduces, reference site A4).
   void schurApply(const T* x, T* q, T* temp, T* w) {
+    ++this->products_;
     spmvEtx(x, temp);
     applyHllInv(temp, w);
     spmvEx(w, q);

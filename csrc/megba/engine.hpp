@@ -97,6 +97,46 @@ class Engine {
 
   // Whether the last solveLinear ended on the relTol rule.
   virtual bool relStopHit() const = 0;
+
+  // ---- several unit columns at once (covariance.hpp, batch > 1) -----------
+  // Most columns solveUnitBatch can carry through one batched Schur product;
+  // 1: the engine has no batched product and runs the column loop below.
+  virtual int maxBatch() const { return 1; }
+
+  // Solve the k unit right-hand sides e_rhsRows[c] from x = 0 and return the
+  // rows readRows[0..n) of every solution: out is n x k row-major, iters and
+  // converged are per column.  COLLECTIVE when worldSize>1.  Overwrites g and
+  // deltaX like setUnitRhs / solveLinear.
+  virtual void solveUnitBatch(const int64_t* rhsRows, int k,
+                              const SolverOptionPCG& opt,
+                              const int64_t* readRows, int n, double* out,
+                              int* iters, uint8_t* converged) {
+    std::vector<double> col(n);
+    for (int c = 0; c < k; ++c) {
+      setUnitRhs(rhsRows[c]);
+      iters[c] = solveLinear(opt);
+      converged[c] = relStopHit();
+      readDeltaXRows(readRows, n, col.data());
+      for (int i = 0; i < n; ++i) out[(size_t)i * k + c] = col[i];
+    }
+  }
+
+  // How often the engine has applied the Schur product S p so far (PCG
+  // iterations and initial residuals; a batched application counts once).
+  int64_t productCount() const { return products_; }
+
+  // Test hook: out = S X for the k columns of X (nc x k row-major, nc =
+  // camDim * ncam), after buildLinearSystem() and processDiag(); inverts the
+  // blocks itself.  batched=false applies the engine's product column by
+  // column, batched=true its batched product (k <= maxBatch()).  COLLECTIVE
+  // when worldSize>1.
+  virtual void schurApplyColumns(const double* /*X*/, int /*k*/,
+                                 bool /*batched*/, double* /*out*/) {
+    MEGBA_CHECK(false, "schur_apply is a hook of the GPU engine");
+  }
+
+ protected:
+  int64_t products_ = 0;
 };
 
 }  // namespace megba

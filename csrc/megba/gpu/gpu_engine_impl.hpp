@@ -34,6 +34,7 @@
 #include "gpu_common.hpp"
 #include "gpu_engine.hpp"
 #include "kernels_assemble.hpp"
+#include "kernels_batch.hpp"
 #include "kernels_forward.hpp"
 #include "kernels_pcg.hpp"
 #include "kernels_prior.hpp"
@@ -268,6 +269,7 @@ class GpuEngine final : public Engine<T> {
 
   ~GpuEngine() override {
     if (hScalar_) (void)hipHostFree(hScalar_);
+    if (bb_.hRho) (void)hipHostFree(bb_.hRho);
     if (pcgGraphExec_) (void)hipGraphExecDestroy(pcgGraphExec_);
     for (void* p : allocs_) (void)hipFree(p);
     if (hasComm_) (void)ncclCommDestroy(comm_);
@@ -405,8 +407,8 @@ class GpuEngine final : public Engine<T> {
             dPtFixed_ ? dPtFixed_ + ptLo_ : nullptr);
   }
 
-  int solveLinear(const SolverOptionPCG& opt) override {
-    // Block inverses (preconditioner replicated; Cinv on the local shard).
+  // Block inverses (preconditioner replicated; Cinv on the local shard).
+  void invertForSolve(const SolverOptionPCG& opt) {
     HIP_CHECK(hipMemsetAsync(dFail_, 0, 2 * sizeof(int), stream_));
     int fail[2] = {0, 0};
     invertBlocks(kInvert<T, CD>, kInvert<T, PD>, fail);
@@ -424,7 +426,10 @@ class GpuEngine final : public Engine<T> {
       invertBlocks(kInvertJitter<T, CD>, kInvertJitter<T, PD>, fail);
       MEGBA_CHECK(!fail[1], "singular Hessian block");
     }
+  }
 
+  int solveLinear(const SolverOptionPCG& opt) override {
+    invertForSolve(opt);
     if (!plan_) plan_ = resolvePlan();
     const T* gc = dG_;
     const T* gp = dG_ + nc_;
@@ -464,15 +469,18 @@ class GpuEngine final : public Engine<T> {
         opt.tol <= 0.0 && opt.refuseRatio >= 1e29 && opt.relTol <= 0.0;
     if (fixedWork) {
       for (; n < opt.maxIter; ++n) {
-        if (pcgGraphExec_)
+        if (pcgGraphExec_) {
           HIP_CHECK(hipGraphLaunch(pcgGraphExec_, stream_));
-        else
+          ++this->products_;  // the replayed body's schurApply
+        } else {
           pcgBody();
+        }
       }
     } else {
       while (!done && n < opt.maxIter) {
         if (pcgGraphExec_) {
           HIP_CHECK(hipGraphLaunch(pcgGraphExec_, stream_));
+          ++this->products_;
         } else {
           pcgBody();
         }
@@ -602,6 +610,285 @@ class GpuEngine final : public Engine<T> {
   }
   bool relStopHit() const override { return relStopHit_; }
 
+  // ---- batched multi-column PCG (kernels_batch.hpp) -------------------------
+  // Compiled for fp64 only (all covariance() can reach), at the widths PD
+  // and CD, for the implicit and the explicit product.
+  int maxBatch() const override {
+    return std::is_same<T, double>::value ? CD : 1;
+  }
+
+  void solveUnitBatch(const int64_t* rhsRows, int k, const SolverOptionPCG& opt,
+                      const int64_t* readRows, int n, double* out, int* iters,
+                      uint8_t* converged) override {
+    // the batched loop has the relTol stop alone: no refuse rule and no
+    // absolute tol, which is how computeCovariance solves
+    const bool plain =
+        opt.refuseRatio >= 1e29 && opt.tol <= 0.0 && opt.relTol > 0.0;
+    if (k < 2 || k > maxBatch() || n <= 0 || !plain) {
+      Engine<T>::solveUnitBatch(rhsRows, k, opt, readRows, n, out, iters,
+                                converged);
+      return;
+    }
+    if constexpr (std::is_same<T, double>::value) {
+      for (int c = 0; c < k; ++c)
+        MEGBA_CHECK(rhsRows[c] >= 0 && rhsRows[c] < dim_,
+                    "unit right-hand side out of range");
+      for (int i = 0; i < n; ++i)
+        MEGBA_CHECK(readRows[i] >= 0 && readRows[i] < dim_,
+                    "deltaX row out of range");
+      dispatchWidth(k, [&](auto kb) {
+        solveBatchW<decltype(kb)::value>(rhsRows, k, opt, readRows, n, out,
+                                         iters, converged);
+      });
+    }
+  }
+
+  void schurApplyColumns(const double* X, int k, bool batched,
+                         double* out) override {
+    MEGBA_CHECK(k >= 1, "schur_apply: X needs at least one column");
+    MEGBA_CHECK(!batched || (maxBatch() > 1 && k <= maxBatch()),
+                "schur_apply: this engine has no batched product of that "
+                "width (max_batch())");
+    invertForSolve(SolverOptionPCG{});
+    if (!batched) {
+      if (!plan_) plan_ = resolvePlan();
+      std::vector<T> col(nc_);
+      for (int c = 0; c < k; ++c) {
+        for (int64_t i = 0; i < nc_; ++i) col[i] = (T)X[i * k + c];
+        up(dV_, col.data(), nc_);
+        schurApply({dV_, false}, dQ_, /*withDot=*/false);
+        sync();
+        const std::vector<double> q = down(dQ_, nc_);
+        for (int64_t i = 0; i < nc_; ++i) out[i * k + c] = q[i];
+      }
+      return;
+    }
+    if constexpr (std::is_same<T, double>::value) {
+      dispatchWidth(k, [&](auto kb) {
+        constexpr int KB = decltype(kb)::value;
+        constexpr int XP = PkJ::XP;
+        ensureBatchBufs(0);
+        std::vector<T> h((size_t)ncam_ * KB * XP, T(0));
+        for (int64_t cam = 0; cam < ncam_; ++cam)
+          for (int c = 0; c < k; ++c)
+            for (int i = 0; i < CD; ++i)
+              h[(cam * KB + c) * XP + i] = (T)X[(cam * CD + i) * k + c];
+        up(bb_.P, h.data(), (int64_t)h.size());
+        schurApplyB<KB>(k);
+        sync();
+        const std::vector<double> q = down(bb_.Q, (int64_t)ncam_ * KB * CD);
+        for (int64_t cam = 0; cam < ncam_; ++cam)
+          for (int c = 0; c < k; ++c)
+            for (int i = 0; i < CD; ++i)
+              out[(cam * CD + i) * k + c] = q[(cam * KB + c) * CD + i];
+      });
+    }
+  }
+
+ private:
+  // Buffers of the batched PCG in the layouts of kernels_batch.hpp, sized for
+  // the widest batch (CD columns) and allocated at the first batched call.
+  struct BatchBufs {
+    T *P{}, *X{};             // [cam][KB][XP]
+    T *R{}, *Z{}, *Q{};       // [cam][KB][CD]
+    T* temp{};                // [pt][KB][PD]
+    T* W{};                   // [pt][KB][4]
+    double *part{}, *partQ{};  // [KB][nbR], [KB][nbQ]
+    double *rho{}, *rhoPrev{};  // per column
+    int* done{};                // per column: frozen
+    int64_t* rhs{};             // the columns' unit rows
+    int64_t* rowIdx{};          // requested rows and their values
+    double* rowOut{};
+    int rowCap = 0;
+    int nbR = 0, nbQ = 0;
+    double* hRho{};  // pinned: the per-iteration readback, then hDone
+    int* hDone{};
+  };
+
+  // f(width tag): the narrowest compiled width that holds k columns.
+  template <typename F>
+  static void dispatchWidth(int k, F&& f) {
+    if (k <= PD)
+      f(std::integral_constant<int, PD>{});
+    else
+      f(std::integral_constant<int, CD>{});
+  }
+  template <typename K, typename... A>
+  void launchGrid(K kernel, dim3 grid, A... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlk), 0, stream_, args...);
+  }
+
+  void ensureBatchBufs(int nRows) {
+    constexpr int KBM = CD;
+    BatchBufs& b = bb_;
+    if (!b.P) {
+      b.nbR = precondGrid();
+      b.nbQ = bApplyDotGrid();
+      b.P = dalloc<T>((int64_t)ncam_ * KBM * PkJ::XP);
+      b.X = dalloc<T>((int64_t)ncam_ * KBM * PkJ::XP);
+      b.R = dalloc<T>((int64_t)ncam_ * KBM * CD);
+      b.Z = dalloc<T>((int64_t)ncam_ * KBM * CD);
+      b.Q = dalloc<T>((int64_t)ncam_ * KBM * CD);
+      b.temp = dalloc<T>((int64_t)npt_ * KBM * PD);
+      b.W = dalloc<T>((int64_t)npt_ * KBM * 4);
+      b.part = dalloc<double>((int64_t)KBM * b.nbR);
+      b.partQ = dalloc<double>((int64_t)KBM * b.nbQ);
+      b.rho = dalloc<double>(KBM);
+      b.rhoPrev = dalloc<double>(KBM);
+      b.done = dalloc<int>(KBM);
+      b.rhs = dalloc<int64_t>(KBM);
+      HIP_CHECK(hipHostMalloc((void**)&b.hRho,
+                              KBM * (sizeof(double) + sizeof(int))));
+      b.hDone = (int*)(b.hRho + KBM);
+    }
+    if (nRows > b.rowCap) {
+      b.rowCap = nRows;
+      b.rowIdx = dalloc<int64_t>(nRows);
+      b.rowOut = dalloc<double>((int64_t)nRows * KBM);
+    }
+  }
+
+  template <int KB>
+  void zeroTempB() {
+    zero(bb_.temp + (int64_t)ptLo_ * KB * PD, (int64_t)npL_ * KB * PD);
+  }
+  // temp = E^T x for the k columns of x ([cam][KB][XP]); temp is zeroed first
+  template <int KB>
+  void etxB(const T* x, int k) {
+    zeroTempB<KB>();
+    if (!implicit_) {
+      launchN(kSpmvEtxB<T, CD, PD, RD, KB>, nL_, nL_, dCamOf_, dPtOf_, dHpl_,
+              x, k, bb_.temp);
+      return;
+    }
+    dispatchBool(hasInfo_, [&](auto infoTag) {
+      launchN(kSpmvEtxPkB<T, CD, PD, RD, decltype(infoTag)::value, KB>, nL_,
+              nL_, dCamOf_, dPtOf_, dJPk_, (const T* const*)dJSlots_, dInfo_,
+              lossKind_, lossD2_, x, k, bb_.temp);
+    });
+  }
+  // W = Cinv temp, Q = E W summed over the ranks
+  template <int KB>
+  void cinvThenExB(int k) {
+    launchN(kCinvPadB<T, PD, KB>, (int64_t)npL_ * KB, npL_,
+            shard(dHllInv_, PP), bb_.temp + (int64_t)ptLo_ * KB * PD, k,
+            bb_.W + (int64_t)ptLo_ * KB * 4);
+    zero(bb_.Q, (int64_t)ncam_ * KB * CD);
+    if (nChunks_ > 0 && implicit_)
+      launch(kSpmvExPkB<T, CD, PD, RD, KB>, nChunks_, 64, 0, nChunks_, dChCam_,
+             dChLo_, dChHi_, dPtOfCam_, dJCamPk_, nL_, bb_.W, k, bb_.Q);
+    else if (nChunks_ > 0)
+      launch(kSpmvExB<T, CD, PD, RD, KB>, nChunks_, 64, 0, nChunks_, dChCam_,
+             dChLo_, dChHi_, dPtOfCam_, dHplCam_, nL_, bb_.W, k, bb_.Q);
+    allreduce(bb_.Q, (int64_t)ncam_ * KB * CD, ncclSum);
+  }
+  // Q = S P for the k columns of P, with the p.q partials: schurApply's
+  // batched sibling, one allreduce of the whole product buffer.
+  template <int KB>
+  void schurApplyB(int k) {
+    ++this->products_;
+    etxB<KB>(bb_.P, k);
+    cinvThenExB<KB>(k);
+    launchGrid(kBApplyDotB<T, CD, KB>, dim3(bb_.nbQ, k), ncam_, dHppD_, bb_.P,
+               bb_.Q, bb_.partQ);
+  }
+
+  // The batched PCG: the rotated body of pcgBodyRotated per column, eager
+  // launches, one readback of the k rho values per iteration.  A column
+  // stops when |rho| < relTol |rho_0|; its iteration count is taken then and
+  // its done flag freezes it (alpha = 0, p kept), so x, r and p no longer
+  // change while the other columns go on.
+  template <int KB>
+  void solveBatchW(const int64_t* rhsRows, int k, const SolverOptionPCG& opt,
+                   const int64_t* readRows, int n, double* out, int* iters,
+                   uint8_t* converged) {
+    invertForSolve(opt);
+    ensureBatchBufs(n);
+    BatchBufs& b = bb_;
+    const int64_t padN = (int64_t)ncam_ * KB * PkJ::XP;
+    const int64_t plainN = (int64_t)ncam_ * KB * CD;
+    bool anyPoint = false;
+    for (int c = 0; c < k; ++c) {
+      b.hDone[c] = 0;
+      iters[c] = 0;
+      converged[c] = 0;
+      anyPoint = anyPoint || rhsRows[c] >= nc_;
+    }
+    HIP_CHECK(hipMemcpyAsync(b.rhs, rhsRows, k * sizeof(int64_t),
+                             hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(b.done, b.hDone, k * sizeof(int),
+                             hipMemcpyHostToDevice, stream_));
+    zero(b.X, padN);
+    zero(b.P, padN);
+    zero(b.R, plainN);
+    if (anyPoint) zeroTempB<KB>();
+    // v = g_c - E Cinv g_p as solveLinear forms it: a camera unit is the same
+    // on every rank and needs no 1 / world
+    launch(kSetUnitsB<T, CD, PD, KB>, 1, 64, 0, k, b.rhs, nc_, ptLo_, ptHi_,
+           b.R, b.temp);
+    if (anyPoint) {
+      cinvThenExB<KB>(k);
+      launchN(kSubAssign<T>, plainN, plainN, b.Q, b.R);
+    }
+    // x = 0: r = v without a product
+    for (int c = 0; c < k; ++c)
+      launch(kSetScalar, 1, 1, 0, b.rhoPrev + c, INFINITY);
+    const dim3 gridR(b.nbR, k), gridQ(b.nbQ, k);
+    launchGrid(kPrecondRhoB<T, CD, KB>, gridR, ncam_, dHppInv_, b.R, b.Z,
+               b.part);
+    std::vector<double> rho0(k, 0.0);
+    int nDone = 0;
+    for (int it = 0; it < opt.maxIter && nDone < k; ++it) {
+      launchGrid(kBetaPB<T, CD, KB>, gridQ, ncam_, b.Z, b.part, b.nbR,
+                 b.rhoPrev, b.done, b.rho, b.P);
+      schurApplyB<KB>(k);
+      launchGrid(kUpdateXRPrecondB<T, CD, KB>, gridR, ncam_, b.rho, b.partQ,
+                 b.nbQ, b.done, b.rhoPrev, b.P, b.Q, b.X, b.R, dHppInv_, b.Z,
+                 b.part);
+      HIP_CHECK(hipMemcpyAsync(b.hRho, b.rho, k * sizeof(double),
+                               hipMemcpyDeviceToHost, stream_));
+      sync();
+      bool changed = false;
+      for (int c = 0; c < k; ++c) {
+        if (b.hDone[c]) continue;
+        const double rho = std::abs(b.hRho[c]);
+        if (it == 0) rho0[c] = rho;
+        iters[c] = it + 1;
+        if (rho < opt.relTol * rho0[c]) {
+          b.hDone[c] = 1;
+          converged[c] = 1;
+          ++nDone;
+          changed = true;
+        }
+      }
+      if (changed && nDone < k)
+        HIP_CHECK(hipMemcpyAsync(b.done, b.hDone, k * sizeof(int),
+                                 hipMemcpyHostToDevice, stream_));
+    }
+    // Back-substitution on the requested rows only (kGatherRowsB).
+    etxB<KB>(b.X, k);
+    HIP_CHECK(hipMemcpyAsync(b.rowIdx, readRows, n * sizeof(int64_t),
+                             hipMemcpyHostToDevice, stream_));
+    const int64_t nOut = (int64_t)n * k;
+    launchN(kGatherRowsB<T, CD, PD, KB>, nOut, n, k, b.rowIdx, b.rhs, b.X,
+            b.temp, dHllInv_, nc_, ptLo_, ptHi_, rank_ == 0, b.rowOut);
+    if (hasComm_)
+      RCCL_CHECK(ncclAllReduce(b.rowOut, b.rowOut, nOut, ncclDouble, ncclSum,
+                               comm_, stream_));
+    HIP_CHECK(hipMemcpyAsync(out, b.rowOut, nOut * sizeof(double),
+                             hipMemcpyDeviceToHost, stream_));
+    sync();
+    if (hasComm_ || world_ == 1) return;
+    if (hostArD_) {
+      hostArD_(out, (size_t)nOut, 's');
+    } else if (hostAr_) {
+      std::vector<T> t(out, out + nOut);
+      hostAr_(t.data(), (size_t)nOut, 's');
+      for (int64_t i = 0; i < nOut; ++i) out[i] = (double)t[i];
+    }
+  }
+
+ public:
   DenseDump dump() const override {
     DenseDump d;
     d.e0 = e0_;
@@ -1364,11 +1651,13 @@ class GpuEngine final : public Engine<T> {
       return;
     }
     bool ok = true;
+    const int64_t productsBefore = this->products_;
     try {
       pcgBody();
     } catch (...) {
       ok = false;
     }
+    this->products_ = productsBefore;  // captured, not applied
     if (hipStreamEndCapture(stream_, &graph) != hipSuccess || !ok || !graph) {
       if (graph) (void)hipGraphDestroy(graph);
       (void)hipGetLastError();
@@ -1422,6 +1711,7 @@ class GpuEngine final : public Engine<T> {
   // x^T q dot partials into the B-apply pass (used by the PCG body) and
   // returns how many partials it wrote to dPartQ_ (0 without withDot).
   int schurApply(XIn x, T* q, bool withDot) {
+    ++this->products_;
     if (withDot && plan_->mergeReduceBApply) {
       schurFusedLdsEcE(x, q, plan_->path, /*bApplyDot=*/true);
       return ldsReduceGrid();
@@ -1500,6 +1790,7 @@ class GpuEngine final : public Engine<T> {
   int rowCap_ = 0;
   std::vector<uint8_t> hCamFixed_, hPtFixed_;  // host copies for isFixed
   bool relStopHit_ = false;
+  BatchBufs bb_;  // batched PCG, allocated at the first batched call
   T *dP_{}, *dRr_{}, *dZ_{}, *dQ_{}, *dV_{}, *dW_{}, *dTemp_{}, *dXBak_{},
       *dXBakPrev_{}, *dPtMerge_{};
   hipGraphExec_t pcgGraphExec_{};

@@ -65,7 +65,7 @@ static BAProblemHost withCentrePriors(const BAProblemHost& raw, double w) {
 
 // Covariance of every camera block and of point 0 through the driver.
 static CovarianceResult viaDriver(const BAProblemHost& prob,
-                                  const ProblemOption& opt) {
+                                  const ProblemOption& opt, int batch = 1) {
   const ProblemIndex ix = buildIndex(prob, 1);
   std::unique_ptr<Engine<double>> eng;
   if (opt.device == Device::CPU)
@@ -74,7 +74,9 @@ static CovarianceResult viaDriver(const BAProblemHost& prob,
     eng = makeGpuEngine<double>(prob, ix, opt, std::string(), nullptr);
   std::vector<int> cams(prob.ncam);
   for (int i = 0; i < prob.ncam; ++i) cams[i] = i;
-  return computeCovariance(*eng, cams, {0});
+  CovarianceOption copt;
+  copt.batch = batch;
+  return computeCovariance(*eng, cams, {0}, copt);
 }
 
 // diag(J_C Sigma_cam J_C^T) of camera i: the variances of its centre.
@@ -165,6 +167,26 @@ int main(int argc, char** argv) {
   std::cout << "graph vs driver: max difference " << diff << " of " << scale
             << "; asymmetry " << covLoose.asymmetry << "\n";
   MEGBA_CHECK(diff <= 1e-9 * scale, "graph and driver covariances differ");
+
+  // --- batched columns ------------------------------------------------------
+  // batch = camDim solves the 9 columns of a camera block together where the
+  // engine has a batched product (the GPU engine's matrix-free mode); any
+  // other engine runs the column loop.  Either way the matrix is the same.
+  ProblemOption optImplicit = opt;
+  optImplicit.schur = SchurMode::IMPLICIT;
+  const CovarianceResult covOne = viaDriver(loose, optImplicit, 1);
+  const CovarianceResult covBatch = viaDriver(loose, optImplicit, raw.camDim);
+  double diffBatch = 0.0;
+  for (size_t i = 0; i < covOne.joint.size(); ++i)
+    diffBatch =
+        std::max(diffBatch, std::fabs(covOne.joint[i] - covBatch.joint[i]));
+  std::cout << "batch=" << raw.camDim << " vs batch=1: max difference "
+            << diffBatch << " of " << scale << "; Schur products "
+            << covBatch.products << " vs " << covOne.products << "\n";
+  MEGBA_CHECK(diffBatch <= 1e-9 * scale,
+              "batched and column-loop covariances differ");
+  MEGBA_CHECK(covBatch.products <= covOne.products,
+              "the batched run applied more Schur products");
 
   for (int i = 0; i < n; ++i)
     MEGBA_CHECK(covLoose.joint[(size_t)i * n + i] > 0.0,

@@ -231,12 +231,12 @@ class GraphProblem:
     def covariance(self, vertices, device="cpu", diff="auto",
                    schur="explicit", loss="none", loss_delta=1.0,
                    custom_forward=None, intrinsics=None, tol=1e-10,
-                   max_iter=2000, strict=True):
+                   max_iter=2000, strict=True, batch=1):
         """Joint marginal covariance of `vertices` (appended CameraVertex /
         PointVertex objects, any order, each once) at their current
         estimations; rows and columns follow the order of `vertices`.  Like
         solve() it builds the problem anew and keeps no engine; see
-        BAProblem.covariance for what the matrix is."""
+        BAProblem.covariance for what the matrix is and what batch does."""
         cams, pts = [], []
         for v in vertices:
             if not isinstance(v, BaseVertex):
@@ -251,7 +251,7 @@ class GraphProblem:
                 loss_delta=loss_delta, custom_forward=custom_forward,
                 intrinsics=intrinsics)
         joint = p.covariance(cams, pts, tol=tol, max_iter=max_iter,
-                             strict=strict)["joint"]
+                             strict=strict, batch=batch)["joint"]
         # array order (cameras first) -> the order of `vertices`
         cd = p.cams.shape[1]
         at, nc, ic, ip = [], cd * len(cams), 0, 0

@@ -110,7 +110,7 @@ class BAProblem:
 
     # -- marginal covariances ------------------------------------------------
     def covariance(self, cam_idx=None, pt_idx=None, tol=1e-10, max_iter=2000,
-                   strict=True):
+                   strict=True, batch=1):
         """Marginal covariance of the given cameras and points at the current
         parameters: the matching sub-matrix of H^-1, H = J^T W J plus the
         prior terms (the Hessian the LM step uses, robust-loss weights and
@@ -131,7 +131,16 @@ class BAProblem:
         "iters" and "converged" per column; "asymmetry",
         max|A - A^T| / max|A| of the raw columns before symmetrising, a free
         accuracy indicator.  strict=True raises if a column did not
-        converge, strict=False returns with the flags set.
+        converge, strict=False returns with the flags set.  "products" counts
+        the Schur products S p the engine applied during the call.
+
+        batch > 1 solves up to that many columns of one vertex block together
+        where the engine has a batched product: the float64 GPU engine with
+        schur="implicit", up to camDim columns (max_batch()).  The columns
+        then share every pass over J and "products" counts a batched
+        application once.  Every other engine (the CPU engine, explicit
+        mode) accepts batch > 1 and solves column by column.  batch=1 is the
+        column loop.
 
         COLLECTIVE when world_size>1: every rank calls it with the same
         arguments and gets the same result.  An LM session in progress
@@ -141,7 +150,7 @@ class BAProblem:
         cams = [] if cam_idx is None else [int(i) for i in cam_idx]
         pts = [] if pt_idx is None else [int(i) for i in pt_idx]
         out = self._core.covariance(cams, pts, tol=tol, max_iter=max_iter,
-                                    strict=strict)
+                                    strict=strict, batch=int(batch))
         joint = out["joint"]
         cd = self.cams.shape[1]
         nc = cd * len(cams)

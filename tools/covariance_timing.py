@@ -4,8 +4,10 @@
 Builds the bench's Venice-shaped synthetic problem (fp64, implicit Schur)
 with a centre prior on every camera (the datum), takes a few LM steps, then
 asks for the covariance of one camera and of one point (9 and 3 unit
-right-hand side Schur PCG solves) at each --tol.  Prints the PCG iterations
-of every column, the milliseconds per vertex block and per PCG iteration
+right-hand side Schur PCG solves) at each --tol and each --batch (columns
+solved together; 1 is the column loop).  Prints the PCG iterations of every
+column, the Schur products applied (a batched application counts once), the
+milliseconds per vertex block, per PCG iteration of a column and per product
 (device synchronised before each clock read) and one JSON line.
 """
 import argparse
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--tol", type=float, nargs="+",
                     default=[1e-10, 1e-8, 1e-6, 1e-4])
     ap.add_argument("--max-iter", type=int, default=2000)
+    ap.add_argument("--batch", type=int, nargs="+", default=[1])
     args = ap.parse_args()
     from bench import MODELS
     from megba_amd import _core
@@ -50,39 +53,49 @@ def main():
     print(f"{args.model}: {len(cams)} cams, {len(pts)} pts, {len(ci)} obs; "
           f"chi2 {log['chi2']:.6g} after {args.lm_steps} LM steps", flush=True)
 
-    def timed(cam_idx, pt_idx, tol):
+    def timed(cam_idx, pt_idx, tol, batch, max_iter=args.max_iter):
         _core.device_synchronize()
         t0 = time.perf_counter()
         cov = p.covariance(cam_idx=cam_idx, pt_idx=pt_idx, tol=tol,
-                           max_iter=args.max_iter, strict=False)
+                           max_iter=max_iter, strict=False, batch=batch)
         _core.device_synchronize()
         return cov, (time.perf_counter() - t0) * 1000
 
-    # the first call pays the Schur path choice of the engine's first solve
-    timed([args.camera], [args.point], args.tol[0])
-    out = dict(model=args.model, max_iter=args.max_iter, results=[])
+    # the first call pays the Schur path choice of the engine's first solve,
+    # the first batched call the allocation of the batched buffers
+    timed([args.camera], [args.point], args.tol[0], 1)
+    for batch in args.batch:
+        timed([args.camera], [args.point], args.tol[0], batch, max_iter=5)
+    out = dict(model=args.model, max_iter=args.max_iter,
+               max_batch=int(p.max_batch()), results=[])
     for tol in args.tol:
         print(f"tol {tol:g} (PCG stops on rho/rho_0 < {tol * tol:g}, or "
               f"after {args.max_iter} iterations)")
-        std = []
-        for name, cams_, pts_ in (("camera", [args.camera], []),
-                                  ("point", [], [args.point])):
-            cov, ms = timed(cams_, pts_, tol)
-            its = [int(i) for i in cov["iters"]]
-            print(f"  {name:6s} iters/column {its}  converged "
-                  f"{int(cov['converged'].sum())}/{len(its)}  asymmetry "
-                  f"{cov['asymmetry']:.3g}")
-            print(f"  {'':6s} {ms:9.1f} ms per block (relinearisation "
-                  f"included), {ms / sum(its):6.3f} ms per PCG iteration",
-                  flush=True)
-            std.append(np.sqrt(np.diag(cov["joint"])))
-            out["results"].append(dict(
-                tol=tol, block=name, iters=its, ms=ms,
-                converged=[bool(c) for c in cov["converged"]],
-                asymmetry=float(cov["asymmetry"])))
-        print("  camera std (aa, t, f, k1, k2):",
-              np.array2string(std[0], precision=4))
-        print("  point std:", np.array2string(std[1], precision=4))
+        for batch in args.batch:
+            std = []
+            for name, cams_, pts_ in (("camera", [args.camera], []),
+                                      ("point", [], [args.point])):
+                cov, ms = timed(cams_, pts_, tol, batch)
+                its = [int(i) for i in cov["iters"]]
+                products = int(cov["products"])
+                print(f"  batch {batch} {name:6s} iters/column {its}  "
+                      f"products {products}  converged "
+                      f"{int(cov['converged'].sum())}/{len(its)}  asymmetry "
+                      f"{cov['asymmetry']:.3g}")
+                print(f"  {'':14s} {ms:9.1f} ms per block (relinearisation "
+                      f"included), {ms / sum(its):6.3f} ms per PCG iteration "
+                      f"of a column, {ms / products:6.3f} ms per product",
+                      flush=True)
+                std.append(np.sqrt(np.diag(cov["joint"])))
+                out["results"].append(dict(
+                    tol=tol, batch=batch, block=name, iters=its, ms=ms,
+                    products=products,
+                    converged=[bool(c) for c in cov["converged"]],
+                    asymmetry=float(cov["asymmetry"])))
+            print(f"  batch {batch} camera std (aa, t, f, k1, k2):",
+                  np.array2string(std[0], precision=4))
+            print(f"  batch {batch} point std:",
+                  np.array2string(std[1], precision=4))
     print(json.dumps(out))
 
 
