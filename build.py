@@ -39,6 +39,8 @@ SOURCES = [
     ("megba/gpu/gpu_dims_933.hip", True),
     ("megba/gpu/gpu_dims_633.hip", True),
     ("megba/gpu/gpu_dims_433.hip", True),
+    # dims-independent dense Cholesky and triangular solves
+    ("megba/gpu/dense_chol.hip", True),
     ("megba/jv/jetvector.hip", True),
     ("bindings.cpp", False),
 ]

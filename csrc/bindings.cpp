@@ -345,7 +345,8 @@ struct PyProblem {
   // Marginal covariance of the given vertices (covariance.hpp).
   py::dict covariance(const std::vector<int>& camIds,
                       const std::vector<int>& ptIds, double tol, int maxIter,
-                      bool strict, int batch) {
+                      bool strict, int batch, const std::string& method,
+                      py::object pivotTol, bool cross) {
     MEGBA_CHECK(engD || engF, "call build() first");
     // H's condition number is about 5e11 already on a 12-camera problem
     MEGBA_CHECK(isDouble, "covariance needs dtype float64");
@@ -354,15 +355,38 @@ struct PyProblem {
     o.maxIter = maxIter;
     o.strict = strict;
     o.batch = batch;
+    if (method != "pcg" && method != "dense")
+      throw py::value_error("megba: covariance method must be pcg|dense");
+    o.method = method == "dense" ? CovarianceMethod::Dense
+                                 : CovarianceMethod::Pcg;
+    if (!pivotTol.is_none()) o.pivotTol = py::cast<double>(pivotTol);
+    o.cross = cross;
     CovarianceResult r;
     {
       py::gil_scoped_release rel;
       r = computeCovariance(*engD, camIds, ptIds, o);
     }
     py::dict d;
-    py::array_t<double> joint({r.n, r.n});
-    std::copy(r.joint.begin(), r.joint.end(), joint.mutable_data());
-    d["joint"] = joint;
+    if (cross) {
+      py::array_t<double> joint({r.n, r.n});
+      std::copy(r.joint.begin(), r.joint.end(), joint.mutable_data());
+      d["joint"] = joint;
+    } else {
+      d["joint"] = py::none();
+      d["blocks"] = py::array_t<double>((py::ssize_t)r.blocks.size(),
+                                        r.blocks.data());
+    }
+    d["method"] = method;
+    d["min_pivot_ratio"] = r.minPivotRatio;
+    d["pivot_tol"] = o.pivotTol;
+    if (o.method == CovarianceMethod::Dense) {
+      py::dict ms;
+      ms["form"] = r.formMs;
+      ms["factor"] = r.factorMs;
+      ms["trailing"] = r.trailingMs;
+      ms["solve"] = r.solveMs;
+      d["dense_ms"] = ms;
+    }
     d["iters"] = py::array_t<int>((py::ssize_t)r.iters.size(), r.iters.data());
     py::array_t<bool> conv((py::ssize_t)r.converged.size());
     for (size_t i = 0; i < r.converged.size(); ++i)
@@ -394,6 +418,38 @@ struct PyProblem {
       engD->schurApplyColumns(X.data(), k, batched, out.mutable_data());
     }
     return out;
+  }
+  // The dense S the engine forms for method="dense" (a test hook).
+  py::array_t<double> denseSchur() {
+    MEGBA_CHECK(engD, "dense_schur needs a built float64 problem");
+    const EngineShape sh = engD->shape();
+    const py::ssize_t n = (py::ssize_t)sh.ncam * sh.camDim;
+    py::array_t<double> out({n, n});
+    {
+      py::gil_scoped_release rel;
+      engD->denseSchurMatrix(out.mutable_data());
+    }
+    return out;
+  }
+  // Cholesky of the caller's matrix with the engine's factorization (a test
+  // hook): (L, fail_row, min_pivot_ratio).
+  py::tuple denseCholesky(
+      py::array_t<double, py::array::c_style | py::array::forcecast> A,
+      py::object pivotTol) {
+    MEGBA_CHECK(engD, "dense_cholesky needs a built float64 problem");
+    MEGBA_CHECK(A.ndim() == 2 && A.shape(0) == A.shape(1) && A.shape(0) >= 1,
+                "dense_cholesky: A must be square");
+    const int n = (int)A.shape(0);
+    py::array_t<double> L({A.shape(0), A.shape(1)});
+    std::copy(A.data(), A.data() + A.size(), L.mutable_data());
+    const double tol = pivotTol.is_none() ? CovarianceOption{}.pivotTol
+                                          : py::cast<double>(pivotTol);
+    DenseFactorInfo info;
+    {
+      py::gil_scoped_release rel;
+      info = engD->denseCholesky(L.mutable_data(), n, tol);
+    }
+    return py::make_tuple(L, info.failRow, info.minPivotRatio);
   }
   void updateParams() {
     withEngine([&](auto& e) { e.updateParams(); return 0; });
@@ -576,8 +632,12 @@ PYBIND11_MODULE(_core, m) {
       .def("covariance", &PyProblem::covariance, py::arg("cam_idx"),
            py::arg("pt_idx"), py::arg("tol") = 1e-10,
            py::arg("max_iter") = 2000, py::arg("strict") = true,
-           py::arg("batch") = 1)
+           py::arg("batch") = 1, py::arg("method") = "pcg",
+           py::arg("pivot_tol") = py::none(), py::arg("cross") = true)
       .def("max_batch", &PyProblem::maxBatch)
+      .def("dense_schur", &PyProblem::denseSchur)
+      .def("dense_cholesky", &PyProblem::denseCholesky, py::arg("A"),
+           py::arg("pivot_tol") = py::none())
       .def("schur_apply", &PyProblem::schurApply, py::arg("X"),
            py::arg("batched") = true)
       .def("update_params", &PyProblem::updateParams)

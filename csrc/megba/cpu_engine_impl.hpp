@@ -11,11 +11,14 @@
 #pragma once
 
 #include "cpu_engine.hpp"
+#include "dense_host.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #ifdef _OPENMP
 #include <omp.h>
 #endif
@@ -516,6 +519,93 @@ class CpuEngine final : public Engine<T> {
   }
   bool relStopHit() const override { return relStopHit_; }
 
+  // ---- dense Cholesky of the Schur complement (dense_host.hpp) -------------
+  DenseFactorInfo denseSchurFactor(double pivotTol) override {
+    const auto t0 = std::chrono::steady_clock::now();
+    formDenseSchur();
+    const auto t1 = std::chrono::steady_clock::now();
+    const int64_t n = (int64_t)ncam_ * CD;
+    DenseFactorInfo info =
+        denseCholeskyHost(denseS_.data(), n, n, pivotTol, nt_);
+    const auto t2 = std::chrono::steady_clock::now();
+    info.formMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    info.factorMs = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    denseReady_ = info.ok;
+    return info;
+  }
+
+  void solveUnitDense(const int64_t* rhsRows, int k, const int64_t* readRows,
+                      int n, double* out) override {
+    MEGBA_CHECK(denseReady_, "solveUnitDense: no dense Schur factor");
+    MEGBA_CHECK(k >= 1 && k <= std::max(CD, PD),
+                "solveUnitDense: too many columns");
+    const int64_t nc = (int64_t)ncam_ * CD;
+    std::vector<T> gp((size_t)npt_ * PD), w((size_t)npt_ * PD), v(nc),
+        temp((size_t)npt_ * PD);
+    std::vector<double> X((size_t)nc * k, 0.0);
+    // v = g_c - E Cinv g_p, column by column
+    for (int c = 0; c < k; ++c) {
+      MEGBA_CHECK(rhsRows[c] >= 0 && rhsRows[c] < dim_,
+                  "unit right-hand side out of range");
+      if (rhsRows[c] < nc) {
+        X[(size_t)rhsRows[c] * k + c] = 1.0;
+        continue;
+      }
+      std::fill(gp.begin(), gp.end(), T(0));
+      if (ownsRow(rhsRows[c])) gp[rhsRows[c] - nc] = T(1);
+      applyHllInv(gp.data(), w.data());
+      spmvEx(w.data(), v.data());
+      if (ar_) ar_(v.data(), nc, 's');
+      for (int64_t i = 0; i < nc; ++i) X[(size_t)i * k + c] = -(double)v[i];
+    }
+    denseCholSolveHost(denseS_.data(), nc, nc, X.data(), k);
+    // the requested rows; a point row is back-substituted by its owner
+    std::vector<T> x(nc);
+    for (int c = 0; c < k; ++c) {
+      for (int64_t i = 0; i < nc; ++i) x[i] = (T)X[(size_t)i * k + c];
+      spmvEtx(x.data(), temp.data());
+      for (int i = 0; i < n; ++i) {
+        const int64_t row = readRows[i];
+        MEGBA_CHECK(row >= 0 && row < dim_, "deltaX row out of range");
+        double val = 0.0;
+        if (row < nc) {
+          if (rank_ == 0) val = X[(size_t)row * k + c];
+        } else if (ownsRow(row)) {
+          const int64_t pt = (row - nc) / PD;
+          T rhs[PD], dx[PD];
+          for (int q = 0; q < PD; ++q)
+            rhs[q] = (rhsRows[c] == nc + pt * PD + q ? T(1) : T(0)) -
+                     temp[PD * pt + q];
+          matVec<T, PD>(&HllInv_[(size_t)pt * PP], rhs, dx);
+          val = (double)dx[(row - nc) % PD];
+        }
+        out[(size_t)i * k + c] = val;
+      }
+    }
+    if (world_ > 1) sumDoubles(out, (size_t)n * k);
+  }
+
+  void releaseDenseSchur() override {
+    std::vector<double>().swap(denseS_);
+    denseReady_ = false;
+  }
+
+  void denseSchurMatrix(double* out) override {
+    formDenseSchur();
+    const int64_t n = (int64_t)ncam_ * CD;
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = 0; j <= i; ++j)
+        out[i * n + j] = out[j * n + i] = denseS_[i * n + j];
+    releaseDenseSchur();
+  }
+
+  DenseFactorInfo denseCholesky(double* A, int n, double pivotTol) override {
+    const DenseFactorInfo info = denseCholeskyHost(A, n, n, pivotTol, nt_);
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = i + 1; j < n; ++j) A[i * n + j] = 0.0;
+    return info;
+  }
+
   DenseDump dump() const override {
     DenseDump d;
     d.e0 = e0_;
@@ -752,6 +842,94 @@ class CpuEngine final : public Engine<T> {
                         row < nc + (int64_t)ptHi_ * PD);
   }
 
+  // Sum a double array over the ranks (the dense route is fp64 only).
+  void sumDoubles(double* v, size_t n) {
+    if (arD_) {
+      arD_(v, n, 's');
+    } else if (ar_) {
+      std::vector<T> t(v, v + n);
+      ar_(t.data(), n, 's');
+      for (size_t i = 0; i < n; ++i) v[i] = (double)t[i];
+    }
+  }
+
+  // W_e = Jc^T L Jp of local edge e ([CD][PD]): the Hpl block, built on the
+  // spot in implicit mode exactly as buildLinearSystem builds it.
+  void edgeW(int64_t e, T* W) {
+    if (!implicit_) {
+      for (int i = 0; i < CP; ++i) W[i] = Hpl_[CP * e + i];
+      return;
+    }
+    T wJc[RD][CD], wJp[RD][PD], wr[RD];
+    weightedRows(e, wJc, wJp, wr);
+    for (int i = 0; i < CD; ++i)
+      for (int j = 0; j < PD; ++j) {
+        T v = T(0);
+        for (int row = 0; row < RD; ++row)
+          v += JcBak_[CR * e + CD * row + i] * wJp[row][j];
+        W[i * PD + j] = v;
+      }
+  }
+
+  // denseS_ = HppD - E Cinv E^T, lower triangle, n = CD * ncam.  Every
+  // thread owns the block rows of its cameras: camera i walks its edges,
+  // and for each of them the point's run up to camera i.  No atomics, and
+  // the same sums in the same order for any thread count.
+  void formDenseSchur() {
+    MEGBA_CHECK((std::is_same<T, double>::value),
+                "the dense Schur route needs dtype float64");
+    invertBlocks(/*refuseJitter=*/true);
+    const int64_t n = (int64_t)ncam_ * CD;
+    denseReady_ = false;
+    denseS_.assign((size_t)n * n, 0.0);
+    if (camEdgePtr_.empty()) {
+      camEdgePtr_.assign(ncam_ + 1, 0);
+      for (int64_t e = 0; e < nL_; ++e) camEdgePtr_[camOf_[e] + 1]++;
+      for (int c = 0; c < ncam_; ++c) camEdgePtr_[c + 1] += camEdgePtr_[c];
+      camEdges_.resize(nL_);
+      std::vector<int64_t> cur(camEdgePtr_.begin(), camEdgePtr_.end() - 1);
+      for (int64_t e = 0; e < nL_; ++e) camEdges_[cur[camOf_[e]]++] = e;
+    }
+#pragma omp parallel for num_threads(nt_) schedule(dynamic, 1)
+    for (int ci = 0; ci < ncam_; ++ci) {
+      for (int64_t s = camEdgePtr_[ci]; s < camEdgePtr_[ci + 1]; ++s) {
+        const int64_t e = camEdges_[s];
+        const int p = ptOf_[e];
+        T W[CP], Y[CP], W2[CP];
+        edgeW(e, W);
+        const T* inv = &HllInv_[(size_t)p * PP];
+        for (int r = 0; r < CD; ++r)
+          for (int q = 0; q < PD; ++q) {
+            T v = T(0);
+            for (int k = 0; k < PD; ++k) v += W[r * PD + k] * inv[k * PD + q];
+            Y[r * PD + q] = v;
+          }
+        for (int64_t e2 = ptRowPtr_[p] - e0_; e2 < ptRowPtr_[p + 1] - e0_;
+             ++e2) {
+          const int cj = camOf_[e2];
+          if (cj > ci) break;  // runs are cam-sorted
+          edgeW(e2, W2);
+          for (int r = 0; r < CD; ++r) {
+            double* row = &denseS_[((size_t)ci * CD + r) * n + (size_t)cj * CD];
+            for (int c = 0; c < CD; ++c) {
+              T v = T(0);
+              for (int q = 0; q < PD; ++q) v += Y[r * PD + q] * W2[c * PD + q];
+              row[c] -= (double)v;
+            }
+          }
+        }
+      }
+    }
+    if (world_ > 1) sumDoubles(denseS_.data(), denseS_.size());
+    // the replicated camera blocks go in once, after the sum
+#pragma omp parallel for num_threads(nt_) schedule(static)
+    for (int c = 0; c < ncam_; ++c)
+      for (int r = 0; r < CD; ++r)
+        for (int k = 0; k <= r; ++k)
+          denseS_[((size_t)c * CD + r) * n + (size_t)c * CD + k] +=
+              (double)HppD_[(size_t)c * CC + r * CD + k];
+  }
+
   // refuseJitter: a failed plain inversion is an error on every rank instead
   // of a retry with a regularised block.
   void invertBlocks(bool refuseJitter) {
@@ -980,6 +1158,10 @@ class CpuEngine final : public Engine<T> {
   std::vector<T> deltaX_, deltaXBak_, gBak_;
   std::vector<T> gSaved_, deltaXSaved_;  // saveLinearState
   bool relStopHit_ = false;
+  // dense Schur route: S, then its Cholesky factor (n x n, lower triangle)
+  std::vector<double> denseS_;
+  bool denseReady_ = false;
+  std::vector<int64_t> camEdgePtr_, camEdges_;  // local edges by camera
   PriorSet camPr_, ctrPr_, ptPr_;  // camera parameter / centre / point priors
   T priorChi2_ = T(0);             // this rank's prior share of the last forward
   std::vector<T> exScratch_, asmScratch_;  // per-thread reduction buffers

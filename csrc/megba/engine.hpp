@@ -23,6 +23,17 @@ struct EngineShape {
   int ncam = 0, npt = 0, camDim = 0, ptDim = 0;
 };
 
+// Outcome of a dense Cholesky factorization (denseSchurFactor).
+struct DenseFactorInfo {
+  bool ok = false;
+  int64_t failRow = -1;         // first failing row in elimination order
+  double minPivotRatio = 1.0;   // min over the factored rows of L_ii^2 / S_ii
+  double failPivotRatio = 0.0;  // that ratio at failRow
+  // wall-clock milliseconds of forming S and of factoring it; trailingMs is
+  // the trailing-update kernel's share where the engine profiles it, else -1
+  double formMs = 0.0, factorMs = 0.0, trailingMs = -1.0;
+};
+
 template <typename T>
 class Engine {
  public:
@@ -119,6 +130,46 @@ class Engine {
       readDeltaXRows(readRows, n, col.data());
       for (int i = 0; i < n; ++i) out[(size_t)i * k + c] = col[i];
     }
+  }
+
+  // ---- dense Cholesky of the Schur complement (covariance.hpp, Dense) ------
+  // After buildLinearSystem() and processDiag(): invert the point blocks
+  // (no jitter: a singular block is an error), form S = HppD - E Cinv E^T
+  // as a dense n x n fp64 matrix, n = camDim * ncam, and factor it in place
+  // as L L^T.  A pivot fails when it is not finite, not positive or below
+  // pivotTol * S_ii; the factor is then unusable.  Costs 8 n^2 bytes until
+  // releaseDenseSchur().  COLLECTIVE when worldSize>1: every rank forms the
+  // partial S of its point shard, the partials are summed and every rank
+  // factors its own copy.  fp64 engines only.
+  virtual DenseFactorInfo denseSchurFactor(double /*pivotTol*/) {
+    MEGBA_CHECK(false, "this engine has no dense Schur factorization");
+    return {};
+  }
+
+  // solveUnitBatch against the stored factor: the k <= max(camDim, ptDim)
+  // unit right-hand sides e_rhsRows[c] solved exactly, rows readRows[0..n) of
+  // every solution into out (n x k row-major).  COLLECTIVE when worldSize>1.
+  virtual void solveUnitDense(const int64_t* /*rhsRows*/, int /*k*/,
+                              const int64_t* /*readRows*/, int /*n*/,
+                              double* /*out*/) {
+    MEGBA_CHECK(false, "this engine has no dense Schur factorization");
+  }
+
+  // Free the n^2 buffer of denseSchurFactor.
+  virtual void releaseDenseSchur() {}
+
+  // Test hooks.  denseSchurMatrix: the S denseSchurFactor would factor, as a
+  // symmetric n x n row-major matrix (after buildLinearSystem() and
+  // processDiag(); COLLECTIVE).  denseCholesky: factor the caller's n x n
+  // symmetric matrix with the engine's factorization; A is overwritten with
+  // L, upper triangle zero.
+  virtual void denseSchurMatrix(double* /*out*/) {
+    MEGBA_CHECK(false, "this engine has no dense Schur factorization");
+  }
+  virtual DenseFactorInfo denseCholesky(double* /*A*/, int /*n*/,
+                                        double /*pivotTol*/) {
+    MEGBA_CHECK(false, "this engine has no dense Schur factorization");
+    return {};
   }
 
   // How often the engine has applied the Schur product S p so far (PCG

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -29,12 +30,14 @@
 #include <vector>
 
 #include "../jv/jetvector.hpp"
+#include "dense_chol.hpp"
 #include "edge_ops.hpp"
 #include "edge_tables.hpp"
 #include "gpu_common.hpp"
 #include "gpu_engine.hpp"
 #include "kernels_assemble.hpp"
 #include "kernels_batch.hpp"
+#include "kernels_dense.hpp"
 #include "kernels_forward.hpp"
 #include "kernels_pcg.hpp"
 #include "kernels_prior.hpp"
@@ -228,6 +231,14 @@ class GpuEngine final : public Engine<T> {
       dChCam_ = upNew(t.chCam);
       dChLo_ = upNew(t.chLo);
       dChHi_ = upNew(t.chHi);
+      // dense Schur route: cam-sorted row range of every camera and the
+      // primary edge range of every local point (uploaded at first use)
+      hCamRow_.assign(ncam_ + 1, 0);
+      for (int64_t e = 0; e < nL_; ++e) hCamRow_[ix.camOf[e0_ + e] + 1]++;
+      for (int c = 0; c < ncam_; ++c) hCamRow_[c + 1] += hCamRow_[c];
+      hPtRow_.resize(npL_ + 1);
+      for (int q = 0; q <= npL_; ++q)
+        hPtRow_[q] = ix.ptRowPtr[ptLo_ + q] - e0_;
     }
     // Run-aligned windows (<=64 edges, whole point runs) for the fused
     // Schur apply; runs longer than 64 edges are flagged and finished by
@@ -271,6 +282,7 @@ class GpuEngine final : public Engine<T> {
     if (hScalar_) (void)hipHostFree(hScalar_);
     if (bb_.hRho) (void)hipHostFree(bb_.hRho);
     if (pcgGraphExec_) (void)hipGraphExecDestroy(pcgGraphExec_);
+    freeDense();
     for (void* p : allocs_) (void)hipFree(p);
     if (hasComm_) (void)ncclCommDestroy(comm_);
     (void)hipStreamDestroy(stream_);
@@ -685,6 +697,89 @@ class GpuEngine final : public Engine<T> {
     }
   }
 
+  // ---- dense Cholesky of the Schur complement -------------------------------
+  // kernels_dense.hpp forms S, dense_chol.hip factors it and solves; fp64.
+  DenseFactorInfo denseSchurFactor(double pivotTol) override {
+    DenseFactorInfo info;
+    if constexpr (std::is_same<T, double>::value) {
+      const auto t0 = std::chrono::steady_clock::now();
+      formDenseSchur();
+      const auto t1 = std::chrono::steady_clock::now();
+      info = factorDense(pivotTol);
+      const auto t2 = std::chrono::steady_clock::now();
+      info.formMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
+      info.factorMs =
+          std::chrono::duration<double, std::milli>(t2 - t1).count();
+      denseReady_ = info.ok;
+    } else {
+      MEGBA_CHECK(false, "the dense Schur route needs dtype float64");
+    }
+    return info;
+  }
+
+  void solveUnitDense(const int64_t* rhsRows, int k, const int64_t* readRows,
+                      int n, double* out) override {
+    MEGBA_CHECK(denseReady_, "solveUnitDense: no dense Schur factor");
+    MEGBA_CHECK(k >= 1 && k <= (CD > PD ? CD : PD) && n > 0,
+                "solveUnitDense: too many columns");
+    for (int c = 0; c < k; ++c)
+      MEGBA_CHECK(rhsRows[c] >= 0 && rhsRows[c] < dim_,
+                  "unit right-hand side out of range");
+    for (int i = 0; i < n; ++i)
+      MEGBA_CHECK(readRows[i] >= 0 && readRows[i] < dim_,
+                  "deltaX row out of range");
+    static_assert((CD > PD ? CD : PD) <= dense::kMaxRhs,
+                  "dense::solve carries at most kMaxRhs columns");
+    if constexpr (std::is_same<T, double>::value) {
+      // solveBatchW with the iteration loop replaced by two substitutions
+      dispatchWidth(k, [&](auto kb) {
+        constexpr int KB = decltype(kb)::value;
+        ensureBatchBufs(n);
+        unitRhsB<KB>(rhsRows, k);
+        dense::solve(dn_.S, dn_.inv, dn_.np, nc_, bb_.R, bb_.X, dn_.work, CD,
+                     KB, k, PkJ::XP, stream_);
+        readRowsB<KB>(k, readRows, n, out);
+      });
+    }
+  }
+
+  void releaseDenseSchur() override { freeDense(); }
+
+  void denseSchurMatrix(double* out) override {
+    if constexpr (std::is_same<T, double>::value) {
+      formDenseSchur();
+      const int64_t np = dn_.np;
+      std::vector<double> h((size_t)np * np);
+      HIP_CHECK(hipMemcpy(h.data(), dn_.S, h.size() * sizeof(double),
+                          hipMemcpyDeviceToHost));
+      freeDense();
+      for (int64_t i = 0; i < nc_; ++i)
+        for (int64_t j = 0; j <= i; ++j)
+          out[i * nc_ + j] = out[j * nc_ + i] = h[i * np + j];
+    } else {
+      MEGBA_CHECK(false, "the dense Schur route needs dtype float64");
+    }
+  }
+
+  DenseFactorInfo denseCholesky(double* A, int n, double pivotTol) override {
+    freeDense();
+    allocDense(n, /*edgeBlocks=*/false);
+    const int64_t np = dn_.np;
+    std::vector<double> h((size_t)np * np, 0.0);
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = 0; j <= i; ++j) h[i * np + j] = A[i * (int64_t)n + j];
+    HIP_CHECK(hipMemcpyAsync(dn_.S, h.data(), h.size() * sizeof(double),
+                             hipMemcpyHostToDevice, stream_));
+    dense::identityTail(dn_.S, np, n, stream_);
+    const DenseFactorInfo info = factorDense(pivotTol);
+    HIP_CHECK(hipMemcpy(h.data(), dn_.S, h.size() * sizeof(double),
+                        hipMemcpyDeviceToHost));
+    freeDense();
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = 0; j < n; ++j) A[i * (int64_t)n + j] = h[i * np + j];
+    return info;
+  }
+
  private:
   // Buffers of the batched PCG in the layouts of kernels_batch.hpp, sized for
   // the widest batch (CD columns) and allocated at the first batched call.
@@ -806,30 +901,15 @@ class GpuEngine final : public Engine<T> {
     ensureBatchBufs(n);
     BatchBufs& b = bb_;
     const int64_t padN = (int64_t)ncam_ * KB * PkJ::XP;
-    const int64_t plainN = (int64_t)ncam_ * KB * CD;
-    bool anyPoint = false;
     for (int c = 0; c < k; ++c) {
       b.hDone[c] = 0;
       iters[c] = 0;
       converged[c] = 0;
-      anyPoint = anyPoint || rhsRows[c] >= nc_;
     }
-    HIP_CHECK(hipMemcpyAsync(b.rhs, rhsRows, k * sizeof(int64_t),
-                             hipMemcpyHostToDevice, stream_));
     HIP_CHECK(hipMemcpyAsync(b.done, b.hDone, k * sizeof(int),
                              hipMemcpyHostToDevice, stream_));
-    zero(b.X, padN);
     zero(b.P, padN);
-    zero(b.R, plainN);
-    if (anyPoint) zeroTempB<KB>();
-    // v = g_c - E Cinv g_p as solveLinear forms it: a camera unit is the same
-    // on every rank and needs no 1 / world
-    launch(kSetUnitsB<T, CD, PD, KB>, 1, 64, 0, k, b.rhs, nc_, ptLo_, ptHi_,
-           b.R, b.temp);
-    if (anyPoint) {
-      cinvThenExB<KB>(k);
-      launchN(kSubAssign<T>, plainN, plainN, b.Q, b.R);
-    }
+    unitRhsB<KB>(rhsRows, k);
     // x = 0: r = v without a product
     for (int c = 0; c < k; ++c)
       launch(kSetScalar, 1, 1, 0, b.rhoPrev + c, INFINITY);
@@ -865,7 +945,37 @@ class GpuEngine final : public Engine<T> {
         HIP_CHECK(hipMemcpyAsync(b.done, b.hDone, k * sizeof(int),
                                  hipMemcpyHostToDevice, stream_));
     }
-    // Back-substitution on the requested rows only (kGatherRowsB).
+    readRowsB<KB>(k, readRows, n, out);
+  }
+
+  // The k unit right-hand sides in R and x = 0 in X:
+  // v = g_c - E Cinv g_p as solveLinear forms it; a camera unit is the same
+  // on every rank and needs no 1 / world.
+  template <int KB>
+  void unitRhsB(const int64_t* rhsRows, int k) {
+    BatchBufs& b = bb_;
+    const int64_t padN = (int64_t)ncam_ * KB * PkJ::XP;
+    const int64_t plainN = (int64_t)ncam_ * KB * CD;
+    bool anyPoint = false;
+    for (int c = 0; c < k; ++c) anyPoint = anyPoint || rhsRows[c] >= nc_;
+    HIP_CHECK(hipMemcpyAsync(b.rhs, rhsRows, k * sizeof(int64_t),
+                             hipMemcpyHostToDevice, stream_));
+    zero(b.X, padN);
+    zero(b.R, plainN);
+    if (anyPoint) zeroTempB<KB>();
+    launch(kSetUnitsB<T, CD, PD, KB>, 1, 64, 0, k, b.rhs, nc_, ptLo_, ptHi_,
+           b.R, b.temp);
+    if (anyPoint) {
+      cinvThenExB<KB>(k);
+      launchN(kSubAssign<T>, plainN, plainN, b.Q, b.R);
+    }
+  }
+
+  // Rows readRows[0..n) of the k solutions in X, summed over the ranks:
+  // back-substitution on the requested rows only (kGatherRowsB).
+  template <int KB>
+  void readRowsB(int k, const int64_t* readRows, int n, double* out) {
+    BatchBufs& b = bb_;
     etxB<KB>(b.X, k);
     HIP_CHECK(hipMemcpyAsync(b.rowIdx, readRows, n * sizeof(int64_t),
                              hipMemcpyHostToDevice, stream_));
@@ -886,6 +996,117 @@ class GpuEngine final : public Engine<T> {
       hostAr_(t.data(), (size_t)nOut, 's');
       for (int64_t i = 0; i < nOut; ++i) out[i] = (double)t[i];
     }
+  }
+
+  // ---- dense Schur route -----------------------------------------------------
+  // Device buffers of the dense route, held from denseSchurFactor to
+  // releaseDenseSchur.
+  struct DenseBufs {
+    int64_t np = 0;            // padded dimension
+    double* S{};               // np x np: S, then its factor L
+    double* inv{};             // inverses of L's diagonal tiles
+    double* diag0{};           // diagonal of S before the elimination
+    double* work{};            // dense::solve scratch
+    dense::FactorWords* words{};
+    double *Wp{}, *Yc{};       // per-edge blocks of kDenseEdgeBlocks
+  };
+
+  void freeDense() {
+    for (void* p : {(void*)dn_.S, (void*)dn_.inv, (void*)dn_.diag0,
+                    (void*)dn_.work, (void*)dn_.words, (void*)dn_.Wp,
+                    (void*)dn_.Yc})
+      if (p) (void)hipFree(p);
+    dn_ = DenseBufs{};
+    denseReady_ = false;
+  }
+
+  // Buffers for an n x n system, after comparing their size with the free
+  // device memory.
+  void allocDense(int64_t n, bool edgeBlocks) {
+    const int64_t np = dense::paddedDim(n);
+    const int64_t kMax = CD > PD ? CD : PD;
+    const int64_t edgeBytes = edgeBlocks ? 2 * nL_ * CP * 8 : 0;
+    const int64_t need = 8 * np * np + 8 * np * dense::kTile +
+                         8 * np * (1 + 2 * kMax) + edgeBytes;
+    size_t freeB = 0, totalB = 0;
+    HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+    MEGBA_CHECK((size_t)need <= freeB,
+                "covariance: the dense Schur complement needs " +
+                    std::to_string(need) + " bytes (8 n^2 with n = " +
+                    std::to_string(n) + ") and the device has " +
+                    std::to_string(freeB) +
+                    " bytes free; use method=\"pcg\"");
+    const auto get = [&](int64_t count) {
+      void* p = nullptr;
+      HIP_CHECK(hipMalloc(&p, (count > 0 ? count : 1) * sizeof(double)));
+      return (double*)p;
+    };
+    dn_.np = np;
+    dn_.S = get(np * np);
+    dn_.inv = get(np * dense::kTile);
+    dn_.diag0 = get(np);
+    dn_.work = get(2 * np * kMax);
+    dn_.words = (dense::FactorWords*)get(4);
+    if (edgeBlocks) {
+      dn_.Wp = get(nL_ * CP);
+      dn_.Yc = get(nL_ * CP);
+    }
+  }
+
+  // dn_.S = HppD - E Cinv E^T (lower triangle, identity tail) after
+  // buildLinearSystem() and processDiag(): this rank's partial, the sum over
+  // the ranks, then the replicated camera blocks once.
+  void formDenseSchur() {
+    SolverOptionPCG noJitter;
+    noJitter.refuseJitter = true;
+    invertForSolve(noJitter);
+    freeDense();
+    allocDense(nc_, /*edgeBlocks=*/true);
+    if (!dCamEdgeRow_) {
+      dCamEdgeRow_ = upNew(hCamRow_);
+      dPtEdgeRow_ = upNew(hPtRow_);
+    }
+    const int64_t np = dn_.np;
+    HIP_CHECK(hipMemsetAsync(dn_.S, 0, np * np * sizeof(double), stream_));
+    if (nL_ > 0) {
+      const T* camPk = implicit_ ? dJCamPk_ : dHplCam_;
+      dispatchBool(implicit_, [&](auto impTag) {
+        launchN(kDenseEdgeBlocks<T, CD, PD, RD, decltype(impTag)::value>, nL_,
+                nL_, dCamPos_, dPtOf_, camPk, dHllInv_, dn_.Wp, dn_.Yc);
+      });
+    }
+    int tile = kDenseTileCams<CD>;
+    if (knobs_.denseTileCams && *knobs_.denseTileCams >= 1 &&
+        *knobs_.denseTileCams < tile)
+      tile = *knobs_.denseTileCams;
+    launch(kDenseSchurForm<CD, PD>, ncam_, kBlk, 0, ncam_, tile, dCamEdgeRow_,
+           dPtOfCam_, dPtEdgeRow_, ptLo_, dCamOf_, dn_.Wp, dn_.Yc, dn_.S, np);
+    if constexpr (std::is_same<T, double>::value)
+      allreduce(dn_.S, np * np, ncclSum);
+    launchN(kDenseAddDiag<T, CD>, (int64_t)ncam_ * CC, ncam_, dHppD_, dn_.S,
+            np);
+    dense::identityTail(dn_.S, np, nc_, stream_);
+    sync();
+  }
+
+  // Factor dn_.S in place and read the outcome back, once.
+  DenseFactorInfo factorDense(double pivotTol) {
+    // MEGBA_DENSE_PROFILE: time the three kernels with events (a sync per
+    // launch, so the factorization as a whole runs slower)
+    float phaseMs[3] = {0, 0, 0};
+    dense::factor(dn_.S, dn_.np, dn_.inv, dn_.diag0, pivotTol, dn_.words,
+                  stream_, knobs_.denseProfile ? phaseMs : nullptr);
+    dense::FactorWords w;
+    HIP_CHECK(hipMemcpyAsync(&w, dn_.words, sizeof(w), hipMemcpyDeviceToHost,
+                             stream_));
+    sync();
+    DenseFactorInfo info;
+    info.ok = w.failRow < 0;
+    info.failRow = w.failRow;
+    info.minPivotRatio = w.minRatio;
+    info.failPivotRatio = w.failRatio;
+    if (knobs_.denseProfile) info.trailingMs = phaseMs[2];
+    return info;
   }
 
  public:
@@ -1791,6 +2012,12 @@ class GpuEngine final : public Engine<T> {
   std::vector<uint8_t> hCamFixed_, hPtFixed_;  // host copies for isFixed
   bool relStopHit_ = false;
   BatchBufs bb_;  // batched PCG, allocated at the first batched call
+  DenseBufs dn_;  // dense Schur route
+  bool denseReady_ = false;
+  std::vector<int> hCamRow_;       // cam-sorted row range of every camera
+  std::vector<int64_t> hPtRow_;    // local edge range of every local point
+  int* dCamEdgeRow_{};
+  int64_t* dPtEdgeRow_{};
   T *dP_{}, *dRr_{}, *dZ_{}, *dQ_{}, *dV_{}, *dW_{}, *dTemp_{}, *dXBak_{},
       *dXBakPrev_{}, *dPtMerge_{};
   hipGraphExec_t pcgGraphExec_{};

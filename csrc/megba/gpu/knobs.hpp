@@ -30,11 +30,16 @@ struct GpuKnobs {
   bool noGraph = false;      // MEGBA_NO_GRAPH: no hipGraph capture
   bool forceRccl = false;    // MEGBA_FORCE_RCCL: world-1 RCCL communicator
   bool tuneVerbose = false;  // MEGBA_TUNE_VERBOSE: report the Schur path
+  // MEGBA_DENSE_PROFILE: time the kernels of the dense Cholesky one by one
+  bool denseProfile = false;
   // numeric knobs: unset = engine default
   std::optional<int64_t> schurLdsMaxBytes;  // MEGBA_SCHUR_LDS_MAX_BYTES (atoll)
   std::optional<int> schurLdsThreads;       // MEGBA_SCHUR_LDS_THREADS (atoi)
   std::optional<int> chunk;                 // MEGBA_CHUNK (atoi)
   std::optional<int> band;                  // MEGBA_BAND (atoi)
+  // MEGBA_DENSE_TILE_CAMS: cameras per LDS row tile of kDenseSchurForm
+  // (lowered in tests so that small problems take several tiles)
+  std::optional<int> denseTileCams;
 
   static GpuKnobs fromEnv() {
     const auto on = [](const char* name) { return getenv(name) != nullptr; };
@@ -58,11 +63,13 @@ struct GpuKnobs {
     k.noGraph = on("MEGBA_NO_GRAPH");
     k.forceRccl = on("MEGBA_FORCE_RCCL");
     k.tuneVerbose = on("MEGBA_TUNE_VERBOSE");
+    k.denseProfile = on("MEGBA_DENSE_PROFILE");
     if (const char* v = getenv("MEGBA_SCHUR_LDS_MAX_BYTES"))
       k.schurLdsMaxBytes = std::atoll(v);
     k.schurLdsThreads = num("MEGBA_SCHUR_LDS_THREADS");
     k.chunk = num("MEGBA_CHUNK");
     k.band = num("MEGBA_BAND");
+    k.denseTileCams = num("MEGBA_DENSE_TILE_CAMS");
     return k;
   }
 };

@@ -226,8 +226,22 @@ class GraphProblem {
     for (int i = 0; i < n; ++i) {
       res.iters[i] = raw.iters[at[i]];
       res.converged[i] = raw.converged[at[i]];
-      for (int j = 0; j < n; ++j)
+      for (int j = 0; copt.cross && j < n; ++j)
         res.joint[(size_t)i * n + j] = raw.joint[(size_t)at[i] * n + at[j]];
+    }
+    if (!copt.cross) {
+      // the vertices' own blocks, one after the other in their order
+      size_t out = 0;
+      ic = ip = 0;
+      for (const BaseVertex* v : vertices) {
+        const bool cam = v->kind == VertexKind::CAMERA;
+        const size_t len = cam ? (size_t)cd * cd : 9;
+        const size_t from = cam ? (size_t)cd * cd * ic++
+                                : (size_t)cd * cd * camIds.size() + 9 * ip++;
+        std::copy(raw.blocks.begin() + from, raw.blocks.begin() + from + len,
+                  res.blocks.begin() + out);
+        out += len;
+      }
     }
     return res;
   }

@@ -7,6 +7,7 @@
 // gauge, and checks that
 //   * the graph API (GraphProblem::covariance) and the driver over an
 //     array-built engine (computeCovariance) give the same matrix,
+//   * the dense Cholesky route (CovarianceMethod::Dense) agrees with the PCG,
 //   * every variance on the diagonal is positive, and
 //   * priors 100x tighter shrink the variance of every camera centre,
 //     J_C Sigma J_C^T with J_C the centre's Jacobian,
@@ -64,8 +65,9 @@ static BAProblemHost withCentrePriors(const BAProblemHost& raw, double w) {
 }
 
 // Covariance of every camera block and of point 0 through the driver.
-static CovarianceResult viaDriver(const BAProblemHost& prob,
-                                  const ProblemOption& opt, int batch = 1) {
+static CovarianceResult viaDriver(
+    const BAProblemHost& prob, const ProblemOption& opt, int batch = 1,
+    CovarianceMethod method = CovarianceMethod::Pcg, bool cross = true) {
   const ProblemIndex ix = buildIndex(prob, 1);
   std::unique_ptr<Engine<double>> eng;
   if (opt.device == Device::CPU)
@@ -76,6 +78,8 @@ static CovarianceResult viaDriver(const BAProblemHost& prob,
   for (int i = 0; i < prob.ncam; ++i) cams[i] = i;
   CovarianceOption copt;
   copt.batch = batch;
+  copt.method = method;
+  copt.cross = cross;
   return computeCovariance(*eng, cams, {0}, copt);
 }
 
@@ -187,6 +191,35 @@ int main(int argc, char** argv) {
               "batched and column-loop covariances differ");
   MEGBA_CHECK(covBatch.products <= covOne.products,
               "the batched run applied more Schur products");
+
+  // --- dense Cholesky of the Schur complement -------------------------------
+  // method = Dense factors the camera system once and solves every column
+  // exactly; it must agree with the PCG result.  With cross = false only the
+  // vertices' own blocks come back.
+  const CovarianceResult covDense =
+      viaDriver(loose, opt, 1, CovarianceMethod::Dense);
+  double diffDense = 0.0;
+  for (size_t i = 0; i < covLoose.joint.size(); ++i)
+    diffDense =
+        std::max(diffDense, std::fabs(covLoose.joint[i] - covDense.joint[i]));
+  std::cout << "dense vs pcg: max difference " << diffDense << " of " << scale
+            << "; min pivot ratio " << covDense.minPivotRatio << "\n";
+  MEGBA_CHECK(diffDense <= 1e-9 * scale, "dense and PCG covariances differ");
+  MEGBA_CHECK(covDense.products == 0, "the dense route applied a product");
+  const CovarianceResult covOwn =
+      viaDriver(loose, opt, 1, CovarianceMethod::Dense, /*cross=*/false);
+  MEGBA_CHECK(covOwn.joint.empty() &&
+                  covOwn.blocks.size() == (size_t)81 * raw.ncam + 9,
+              "cross = false must return the blocks alone");
+  double diffOwn = 0.0;
+  for (int c = 0; c < raw.ncam; ++c)
+    for (int r = 0; r < 9; ++r)
+      for (int k = 0; k < 9; ++k)
+        diffOwn = std::max(
+            diffOwn,
+            std::fabs(covOwn.blocks[(size_t)81 * c + 9 * r + k] -
+                      covDense.joint[(size_t)(9 * c + r) * n + 9 * c + k]));
+  MEGBA_CHECK(diffOwn <= 1e-12 * scale, "cross = false blocks differ");
 
   for (int i = 0; i < n; ++i)
     MEGBA_CHECK(covLoose.joint[(size_t)i * n + i] > 0.0,

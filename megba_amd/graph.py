@@ -231,12 +231,15 @@ class GraphProblem:
     def covariance(self, vertices, device="cpu", diff="auto",
                    schur="explicit", loss="none", loss_delta=1.0,
                    custom_forward=None, intrinsics=None, tol=1e-10,
-                   max_iter=2000, strict=True, batch=1):
+                   max_iter=2000, strict=True, batch=1, method="pcg",
+                   pivot_tol=None, cross=True):
         """Joint marginal covariance of `vertices` (appended CameraVertex /
         PointVertex objects, any order, each once) at their current
         estimations; rows and columns follow the order of `vertices`.  Like
         solve() it builds the problem anew and keeps no engine; see
-        BAProblem.covariance for what the matrix is and what batch does."""
+        BAProblem.covariance for what the matrix is and what batch, method
+        and pivot_tol do.  With cross=False there is no joint matrix: the
+        result is the list of the vertices' own blocks, in their order."""
         cams, pts = [], []
         for v in vertices:
             if not isinstance(v, BaseVertex):
@@ -250,8 +253,13 @@ class GraphProblem:
         p.build(device=device, diff=diff, schur=schur, loss=loss,
                 loss_delta=loss_delta, custom_forward=custom_forward,
                 intrinsics=intrinsics)
-        joint = p.covariance(cams, pts, tol=tol, max_iter=max_iter,
-                             strict=strict, batch=batch)["joint"]
+        cov = p.covariance(cams, pts, tol=tol, max_iter=max_iter,
+                           strict=strict, batch=batch, method=method,
+                           pivot_tol=pivot_tol, cross=cross)
+        if not cross:
+            own = {CAMERA: iter(cov["cam_cov"]), POINT: iter(cov["pt_cov"])}
+            return [next(own[v.kind]) for v in vertices]
+        joint = cov["joint"]
         # array order (cameras first) -> the order of `vertices`
         cd = p.cams.shape[1]
         at, nc, ic, ip = [], cd * len(cams), 0, 0

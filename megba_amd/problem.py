@@ -110,7 +110,8 @@ class BAProblem:
 
     # -- marginal covariances ------------------------------------------------
     def covariance(self, cam_idx=None, pt_idx=None, tol=1e-10, max_iter=2000,
-                   strict=True, batch=1):
+                   strict=True, batch=1, method="pcg", pivot_tol=None,
+                   cross=True):
         """Marginal covariance of the given cameras and points at the current
         parameters: the matching sub-matrix of H^-1, H = J^T W J plus the
         prior terms (the Hessian the LM step uses, robust-loss weights and
@@ -142,18 +143,49 @@ class BAProblem:
         mode) accepts batch > 1 and solves column by column.  batch=1 is the
         column loop.
 
+        method="dense" forms the camera system S = B - E C^-1 E^T as a dense
+        matrix, factors it once with a Cholesky and solves every column
+        exactly: no tol / max_iter to guess (tol, max_iter and batch are
+        ignored), "iters" all 0, "converged" all True, "products" 0.  It
+        costs 8 * (camDim * ncam)^2 bytes while the call runs; prefer it
+        with few cameras, a tight tolerance or many requested vertices.  A
+        pivot below pivot_tol * S_ii (default sqrt(eps) ~ 1.5e-8) fails the
+        factorization: strict=True raises "not positive definite",
+        strict=False returns "converged" all False and NaN entries.  Unlike
+        the PCG, which without a datum still converges on the intrinsics
+        columns, the dense route then reports the whole system singular.
+        "min_pivot_ratio" is the smallest L_ii^2 / S_ii (NaN for "pcg"),
+        "method" the route taken.
+
+        cross=False solves every block against its own rows only: "joint"
+        is None, "cam_cov" / "pt_cov" are filled from the per-block solves
+        and "asymmetry" is taken over the blocks.  Use it for the covariance
+        of many vertices, where "joint" itself would be large.
+
         COLLECTIVE when world_size>1: every rank calls it with the same
         arguments and gets the same result.  An LM session in progress
         (lm_init / lm_step) continues unchanged afterwards."""
         if not self._built:
             raise RuntimeError("megba: call build() first")
+        if method not in ("pcg", "dense"):
+            raise ValueError("megba: covariance method must be 'pcg' or "
+                             f"'dense', not {method!r}")
         cams = [] if cam_idx is None else [int(i) for i in cam_idx]
         pts = [] if pt_idx is None else [int(i) for i in pt_idx]
         out = self._core.covariance(cams, pts, tol=tol, max_iter=max_iter,
-                                    strict=strict, batch=int(batch))
+                                    strict=strict, batch=int(batch),
+                                    method=method, pivot_tol=pivot_tol,
+                                    cross=bool(cross))
         joint = out["joint"]
         cd = self.cams.shape[1]
         nc = cd * len(cams)
+        if joint is None:
+            blocks = out.pop("blocks")
+            out["cam_cov"] = blocks[:cd * cd * len(cams)].reshape(
+                len(cams), cd, cd).copy()
+            out["pt_cov"] = blocks[cd * cd * len(cams):].reshape(
+                len(pts), 3, 3).copy()
+            return out
         out["cam_cov"] = np.array(
             [joint[cd * i:cd * (i + 1), cd * i:cd * (i + 1)]
              for i in range(len(cams))]).reshape(len(cams), cd, cd)

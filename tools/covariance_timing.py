@@ -9,6 +9,17 @@ solved together; 1 is the column loop).  Prints the PCG iterations of every
 column, the Schur products applied (a batched application counts once), the
 milliseconds per vertex block, per PCG iteration of a column and per product
 (device synchronised before each clock read) and one JSON line.
+
+--method dense takes the dense Cholesky route instead: it prints the
+milliseconds of forming S and of factoring it with the achieved TF/s
+(n^3 / 3 flops), the milliseconds per camera block and per point block of the
+solves, min_pivot_ratio and the standard deviations; --tol and --batch do not
+apply.  With MEGBA_DENSE_PROFILE=1 the share of the trailing-update kernel is
+printed too (the kernels are then timed one by one, which slows the
+factorization as a whole).  --all-cameras adds cross=False over every camera
+and prints the total.  --formation times forming S with the dense kernels
+against building it from ncam applications of the batched product on unit
+columns (schur_apply(batched=True)).
 """
 import argparse
 import json
@@ -33,6 +44,9 @@ def main():
                     default=[1e-10, 1e-8, 1e-6, 1e-4])
     ap.add_argument("--max-iter", type=int, default=2000)
     ap.add_argument("--batch", type=int, nargs="+", default=[1])
+    ap.add_argument("--method", choices=["pcg", "dense"], default="pcg")
+    ap.add_argument("--all-cameras", action="store_true")
+    ap.add_argument("--formation", action="store_true")
     args = ap.parse_args()
     from bench import MODELS
     from megba_amd import _core
@@ -60,6 +74,10 @@ def main():
                            max_iter=max_iter, strict=False, batch=batch)
         _core.device_synchronize()
         return cov, (time.perf_counter() - t0) * 1000
+
+    if args.method == "dense":
+        dense_report(p, _core, args, len(cams))
+        return
 
     # the first call pays the Schur path choice of the engine's first solve,
     # the first batched call the allocation of the batched buffers
@@ -96,6 +114,69 @@ def main():
                   np.array2string(std[0], precision=4))
             print(f"  batch {batch} point std:",
                   np.array2string(std[1], precision=4))
+    print(json.dumps(out))
+
+
+def dense_report(p, _core, args, ncam):
+    cd = p.cams.shape[1]
+    n = cd * ncam
+    flops = n ** 3 / 3
+
+    def timed(**kw):
+        _core.device_synchronize()
+        t0 = time.perf_counter()
+        cov = p.covariance(method="dense", **kw)
+        _core.device_synchronize()
+        return cov, (time.perf_counter() - t0) * 1000
+
+    # strict=True at the defaults: the call that raises on the PCG route
+    timed(cam_idx=[args.camera], pt_idx=[args.point])  # allocations
+    cov, ms = timed(cam_idx=[args.camera], pt_idx=[args.point])
+    d = cov["dense_ms"]
+    out = dict(model=args.model, method="dense", n=n, call_ms=ms,
+               form_ms=d["form"], factor_ms=d["factor"],
+               factor_tflops=flops / d["factor"] * 1e-9,
+               min_pivot_ratio=float(cov["min_pivot_ratio"]))
+    print(f"dense: n = {n}, S holds {8 * n * n / 1e9:.2f} GB; camera "
+          f"{args.camera} and point {args.point} in {ms:.1f} ms "
+          "(relinearisation included)")
+    print(f"  formation {d['form']:.1f} ms, factorization {d['factor']:.1f} "
+          f"ms = {out['factor_tflops']:.2f} TF/s, solves {d['solve']:.1f} ms, "
+          f"min pivot ratio {cov['min_pivot_ratio']:.3g}")
+    if d["trailing"] >= 0:
+        out["trailing_ms"] = d["trailing"]
+        print(f"  trailing update {d['trailing']:.1f} ms of the profiled "
+              f"factorization = {flops / d['trailing'] * 1e-9:.2f} TF/s")
+    for name, kw in (("camera", dict(cam_idx=[args.camera])),
+                     ("point", dict(pt_idx=[args.point]))):
+        c, _ = timed(**kw)
+        out[name + "_block_ms"] = c["dense_ms"]["solve"]
+        print(f"  {name} block {c['dense_ms']['solve']:.2f} ms; std",
+              np.array2string(np.sqrt(np.diag(c["joint"])), precision=4))
+    if args.all_cameras:
+        c, ms = timed(cam_idx=list(range(ncam)), cross=False)
+        out["all_cameras_ms"] = ms
+        out["all_cameras_solve_ms"] = c["dense_ms"]["solve"]
+        print(f"  all {ncam} cameras, cross=False: {ms:.1f} ms in all, "
+              f"{c['dense_ms']['solve']:.1f} ms of it in the solves")
+    if args.formation:
+        p.forward()
+        p.accept_forward()
+        p.build_linear_system()
+        p.process_diag(np.inf)
+        X = np.zeros((n, cd))
+        p.schur_apply(X, batched=True)  # allocations, path choice
+        _core.device_synchronize()
+        t0 = time.perf_counter()
+        for c in range(ncam):
+            X[:] = 0.0
+            X[cd * c:cd * c + cd] = np.eye(cd)
+            p.schur_apply(X, batched=True)
+        _core.device_synchronize()
+        out["products_ms"] = (time.perf_counter() - t0) * 1000
+        print(f"  S from {ncam} batched products on unit columns: "
+              f"{out['products_ms']:.1f} ms (host copies of the columns "
+              f"included) against {d['form']:.1f} ms for the dense kernels")
     print(json.dumps(out))
 
 
